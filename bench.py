@@ -7,6 +7,16 @@ per GPU: Model forward (10 fused TCN_GCN_units on the HIP path), CrossEntropy, b
 Inputs are resident in HBM before the timed region. Weak scaling: 64 clips per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ntu|mp|ens] [--graph 0|1]
+                    [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints its line. --full adds the legs
+that take runs of their own after the timed region: the per-class roofline steps
+(--roofline 0 drops them) and the CPU baseline (--cpu-baseline 0 drops it); without --full
+both fields of the line are null.
+--dump-outputs DIR: after the timed steps, what the last timed step left to its caller is
+written as DIR/<name>.npy (rank 0; float32, float64 where the path computes in float64):
+the loss, every parameter, gradient and buffer of the model (training configs) or the fused
+scores and logits (--config ens). Inputs and initial weights are seeded, so two runs with
+the same arguments compute on the same data.
 --config ens: BASELINE config 4 instead (4-stream MediaPipe ensemble inference, bs=256,
 eval mode, one hipGraph per batch): windows/s, its own JSON line.
 N>1: `python bench.py --gpus N` starts N ranks itself (one process per GPU, through
@@ -14,7 +24,7 @@ torch.distributed.run as a child process, before anything touches a GPU), or run
 an explicit launcher: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N;
 a launcher's WORLD_SIZE that differs from --gpus is an error (exit 2).
 
-Prints ONE JSON line on rank 0 (value = whole-job clips/s), with:
+Prints ONE JSON line on rank 0 (value = whole-job clips/s), under --full with:
   roofline     — dominant kernel class of the timed region, achieved algorithmic
                  FLOP/s (or bytes/s) from HIP events around every launch of it;
   cpu_baseline — the PyTorch-eager CPU restatement (oracle/, "port") on the host cores,
@@ -109,14 +119,66 @@ def parse():
     ap.add_argument("--graph", type=int, default=0, help="capture the step in a hipGraph")
     ap.add_argument("--graph-ens", type=int, default=1,
                     help="--config ens: replay the ensemble forward as one hipGraph")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
-    ap.add_argument("--roofline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that follow the timed region: the per-class "
+                         "roofline steps and the CPU baseline")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="under --full: 0 drops the CPU baseline")
+    ap.add_argument("--roofline", type=int, default=1,
+                    help="under --full: 0 drops the roofline steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step left to its caller as DIR/<name>.npy")
     ap.add_argument("--data", default=None,
                     help="on-disk (N,3,T,V,M) float32 .npy clips (feeders/feeder.py format), "
                          "memory-mapped and streamed to the GPU by shiftgcn.feeder; default: "
                          "one synthetic batch resident in HBM")
     ap.add_argument("--labels", default=None, help="(sample_name, label) pickle for --data")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.cpu_baseline = args.roofline = 0
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, named):
+    """Write ``named`` ([(name, tensor)]) as ``path/<name>.npy``: float32, or float64 for
+    what is not float32 on the device (the ensemble's float64 scores, integer counters).
+    Above DUMP_MAX_BYTES in all, every array is cut to the same fraction of its elements,
+    a sorted sample of its flattened form drawn with a fixed seed."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = []
+    for name, t in named:
+        t = t.detach()
+        t = t.to("cpu", torch.float32 if t.dtype in (torch.float32, torch.float16,
+                                                     torch.bfloat16) else torch.float64)
+        arrays.append((name, t.numpy()))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_MAX_BYTES:
+        frac = 0.98 * DUMP_MAX_BYTES / total
+        rng = np.random.default_rng(0)
+        arrays = [(name, a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * frac)),
+                                                          replace=False))])
+                  for name, a in arrays]
+    for name, a in arrays:
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def model_outputs(model, loss):
+    """What one training step leaves to its caller: the loss it returns, and the model it
+    updated in place (parameters, their gradients, buffers such as the BatchNorm running
+    statistics)."""
+    out = [("loss", loss.reshape(1))]
+    for k, p in model.named_parameters():
+        out.append(("param." + k, p))
+        if p.grad is not None:
+            out.append(("grad." + k, p.grad))
+    out += [("buffer." + k, b) for k, b in model.named_buffers()]
+    return out
 
 
 def host_threads():
@@ -341,8 +403,11 @@ def main():
             step()
         torch.cuda.current_stream().wait_stream(s)
         with torch.cuda.graph(g):
-            step()
-        runner = g.replay
+            graph_loss = step()
+
+        def runner():
+            g.replay()
+            return graph_loss
 
     if sync is not None and not args.graph:
         sync.timing(True)   # HIP events around each timed step's all_reduce
@@ -351,11 +416,13 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        runner()
+        loss = runner()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # before any later leg steps the model again
+        dump_outputs(args.dump_outputs, model_outputs(model, loss))
     rank_ms = [round(1000.0 * elapsed / args.steps, 3)]
     if distributed:
         elapsed, rank_ms = _max_over_ranks(elapsed, dev, world, args.steps)
@@ -611,11 +678,13 @@ def bench_ensemble(args, dev, rank, world, distributed):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        call()
+        scores, logits = call()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("scores", scores), ("logits", logits)])
     rank_ms = [round(1000.0 * elapsed / args.steps, 3)]
     if distributed:
         elapsed, rank_ms = _max_over_ranks(elapsed, dev, world, args.steps)

@@ -123,7 +123,7 @@ def test_bench_two_ranks_same_device():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--batch", "4", "--cpu-baseline", "0"]
+           "--warmup", "1", "--batch", "4", "--full", "--cpu-baseline", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -11,7 +11,7 @@ for c in ${CONFIGS:-ntu}; do
   for i in $(seq 1 ${REPS:-2}); do
     for v in base tree; do
       if [ $v = base ]; then export SGCN_LIB_PATH=$ROOT/tools/ab/libshiftgcn_hip_base.so; else unset SGCN_LIB_PATH; fi
-      timeout -k 10 300 python -u bench.py --cpu-baseline 0 --config $c ${BENCH_ARGS} > $OUT/${c}_${v}$i.log 2>&1 || { tail -20 $OUT/${c}_${v}$i.log; exit 1; }
+      timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --config $c ${BENCH_ARGS} > $OUT/${c}_${v}$i.log 2>&1 || { tail -20 $OUT/${c}_${v}$i.log; exit 1; }
       python -c "
 import json
 d=json.loads(open('$OUT/${c}_${v}$i.log').read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for i in $(seq 1 ${REPS:-3}); do
     for e in none ${ENVS}; do
       if [ $v = tree ]; then unset SGCN_LIB_PATH; else export SGCN_LIB_PATH=$ROOT/tools/ab/libshiftgcn_hip_$v.so; fi
       if [ $e = none ]; then envp=""; else envp="$e"; fi
-      env $envp timeout -k 10 300 python $ROOT/bench.py --cpu-baseline 0 ${BENCH_ARGS} > $OUT/${v}_${e//=/}_$i.log 2>&1 || { tail -20 $OUT/${v}_${e//=/}_$i.log; exit 1; }
+      env $envp timeout -k 10 300 python $ROOT/bench.py --full --cpu-baseline 0 ${BENCH_ARGS} > $OUT/${v}_${e//=/}_$i.log 2>&1 || { tail -20 $OUT/${v}_${e//=/}_$i.log; exit 1; }
       python -c "import json;d=json.loads(open('$OUT/${v}_${e//=/}_$i.log').read().strip().splitlines()[-1]);print('$v','$e',d['value'],d['ms_per_step'],d['roofline']['step_breakdown_ms'] if d['roofline'] else '')" | tee -a $OUT/summary.txt
     done
   done

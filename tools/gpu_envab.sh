@@ -14,7 +14,7 @@ for i in $(seq 1 ${REPS:-2}); do
     name=${s%%:*}
     envs=${s#*:}
     envp=${envs//,/ }
-    env $envp timeout -k 10 300 python $ROOT/bench.py --cpu-baseline 0 ${BENCH_ARGS} > $OUT/${name}_$i.log 2>&1 || { tail -20 $OUT/${name}_$i.log; exit 1; }
+    env $envp timeout -k 10 300 python $ROOT/bench.py --full --cpu-baseline 0 ${BENCH_ARGS} > $OUT/${name}_$i.log 2>&1 || { tail -20 $OUT/${name}_$i.log; exit 1; }
     python -c "
 import json
 d=json.loads(open('$OUT/${name}_$i.log').read().strip().splitlines()[-1])

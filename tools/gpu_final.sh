@@ -12,13 +12,13 @@ if [ "${TESTS:-1}" = "1" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $OUT/gpu_tests.log 2>&1 || { tail -30 $OUT/gpu_tests.log; exit 1; }
   tail -1 $OUT/gpu_tests.log
 fi
-timeout -k 10 400 python -u bench.py > $OUT/bench_ntu.log 2>&1 || { tail -20 $OUT/bench_ntu.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench_ntu.log 2>&1 || { tail -20 $OUT/bench_ntu.log; exit 1; }
 tail -1 $OUT/bench_ntu.log > $OUT/bench_ntu.json
 echo "NTU $(cut -c1-120 $OUT/bench_ntu.json)"
-timeout -k 10 400 python -u bench.py --config mp > $OUT/bench_mp.log 2>&1 || { tail -20 $OUT/bench_mp.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full --config mp > $OUT/bench_mp.log 2>&1 || { tail -20 $OUT/bench_mp.log; exit 1; }
 tail -1 $OUT/bench_mp.log > $OUT/bench_mp.json
 echo "MP $(cut -c1-120 $OUT/bench_mp.json)"
-timeout -k 10 400 python -u bench.py --config ens > $OUT/bench_ens.log 2>&1 || { tail -20 $OUT/bench_ens.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full --config ens > $OUT/bench_ens.log 2>&1 || { tail -20 $OUT/bench_ens.log; exit 1; }
 tail -1 $OUT/bench_ens.log > $OUT/bench_ens.json
 echo "ENS $(cut -c1-120 $OUT/bench_ens.json)"
 cd /tmp && export TMPDIR=/tmp

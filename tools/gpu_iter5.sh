@@ -13,6 +13,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout
 tail -2 $OUT/tests.log
 if [ -n "$NOBENCH" ]; then exit 0; fi
 for c in ntu mp ens; do
-  timeout -k 10 300 python -u bench.py --cpu-baseline 0 --config $c > $OUT/bench_$c.log 2>&1 || { tail -20 $OUT/bench_$c.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --config $c > $OUT/bench_$c.log 2>&1 || { tail -20 $OUT/bench_$c.log; exit 1; }
   python -c "import json,sys; d=json.loads(open('$OUT/bench_$c.log').read().strip().splitlines()[-1]); print('$c', d['value'], d['unit'], d['roofline']['frac'] if d['roofline'] else None)"
 done

@@ -10,7 +10,7 @@ cd $ROOT
 for i in $(seq 1 ${REPS:-2}); do
   for v in base ${LIBS}; do
     if [ $v = base ]; then L=$ROOT/tools/ab/libshiftgcn_hip_base.so; else L=$ROOT/tools/ab/lib_$v.so; fi
-    SGCN_LIB_PATH=$L timeout -k 10 300 python -u bench.py --cpu-baseline 0 --config ${CONFIG:-ntu} > $OUT/${v}_$i.log 2>&1 || { tail -20 $OUT/${v}_$i.log; exit 1; }
+    SGCN_LIB_PATH=$L timeout -k 10 300 python -u bench.py --full --cpu-baseline 0 --config ${CONFIG:-ntu} > $OUT/${v}_$i.log 2>&1 || { tail -20 $OUT/${v}_$i.log; exit 1; }
     python -c "
 import json
 d=json.loads(open('$OUT/${v}_$i.log').read().strip().splitlines()[-1])
