@@ -22,7 +22,7 @@ extern "C" {
 #endif
 
 #define SGCN_EINVAL (-22)
-#define SGCN_ABI_VERSION 23
+#define SGCN_ABI_VERSION 24
 /* Set in sgcn_abi_version()'s value by a diagnostic build (SGCN_PW_DIAG, SGCN_PW_STAMPS,
  * SGCN_DIAG_*: timing probes whose results are WRONG, `make diag` only); the Python loader
  * refuses such a library. */
@@ -42,7 +42,13 @@ extern "C" {
  * default kernels' argument lists.
  * 23: sgcn_sgd_step flags bit 2 (the (weight_decay, lr) column as the device address of a
  * float pair: hyper-parameters of a graph-captured step read at replay); sgcn_pw_fwd_tshift
- * takes two_row (the two-tap operand of channels with |xpos| < 2^-25). */
+ * takes two_row (the two-tap operand of channels with |xpos| < 2^-25).
+ * 24: a unit's output gradient may arrive with its ReLU mask already applied, or as one
+ * value per plane, so its backward never reads its output for the mask alone:
+ * sgcn_gcn_dx_finish takes flags (SGCN_DXF_MASK_DX: dx stored as dx * (x0 > 0);
+ * SGCN_DXF_ADD2_PLANE: add2 is (B*C)); sgcn_tshift_bwd_bnin accepts y = NULL (dy already
+ * masked) and takes dy_plane; sgcn_bn_bwd_reduce takes dy_plane; sgcn_pool_bwd_planes (the
+ * pool gradient's (N*M, C) plane values). */
 int sgcn_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -99,11 +105,15 @@ int sgcn_tshift_fwd_tail(const float* in, float* out, const float* xpos, const f
  * from sgcn_bn_bwd_finalize. That gradient tensor is never written. Plane limits:
  * H*W <= 16384, W <= 64, <= 32 elements per thread of the joint-aligned stride (NT / W) * W,
  * NT = 256 (H*W <= 4096) or 512 (else SGCN_EINVAL: use sgcn_bn_bwd_apply +
- * sgcn_tshift_bwd). */
+ * sgcn_tshift_bwd).
+ * y = NULL (ABI 24): dy already carries the mask (dy = dout * (out > 0), stored by the next
+ * unit's sgcn_gcn_dx_finish with SGCN_DXF_MASK_DX): gout = k1*dy + k2*s + k3 and no y plane
+ * is loaded. dy_plane != 0 (ABI 24): dy is (B*C), one value per plane (a pooled output's
+ * gradient, sgcn_pool_bwd_planes), instead of (B, C, H, W). */
 int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const float* coef,
                          const float* in, const float* xpos, const float* ypos, float* gin,
                          float* gx, float* gy, void* ws, size_t ws_bytes, int B, int C, int H,
-                         int W, int ypos_is_raw, void* stream);
+                         int W, int ypos_is_raw, int dy_plane, void* stream);
 /* Workspace bytes for sgcn_tshift_bwd (B*C float2 plane partials). */
 size_t sgcn_tshift_bwd_ws_bytes(int B, int C);
 
@@ -286,11 +296,15 @@ int sgcn_bn_apply(const float* x, const float* scale, const float* shift, int pe
  * rpart[b][c] likewise for a BatchNorm2d residual input r (NULL = none).
  * dy_coef (optional, [3][C], requires relu): dy is replaced by k1[c]*dy + k2[c]*y + k3[c],
  * i.e. the input gradient of the following BatchNorm2d (whose input is y), computed on the
- * fly instead of materialised (Shift_tcn.bn's dx feeding Shift_gcn's ReLU/BN backward). */
+ * fly instead of materialised (Shift_tcn.bn's dx feeding Shift_gcn's ReLU/BN backward).
+ * relu = 0 takes y = NULL (with sgcn_bn_bwd_apply likewise: a dy that already carries the
+ * ReLU mask, see sgcn_gcn_dx_finish). dy_plane != 0 (ABI 24): dy is (B*C), one value per
+ * plane. */
 int sgcn_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* x,
                        const float* mean, const float* invstd, int per_joint, const float* r,
                        const float* rmean, const float* rinvstd, const float* dy_coef,
-                       float* part, float* rpart, int B, int C, int T, int V, void* stream);
+                       float* part, float* rpart, int B, int C, int T, int V, int dy_plane,
+                       void* stream);
 
 /* dgamma/dbeta (+)= sums (reference feature order); coef[3][F] = {k1, k2, k3} such that
  * dx = k1*g + k2*x + k3: the training-mode BatchNorm input gradient (batch_stats = 1), or
@@ -336,11 +350,19 @@ int sgcn_gcn_gather(const float* x0, const float* m, float* xg, int B, int C, in
  * g = dx*(x0 > 0), xhat = (prev_s - prev_mean[c])*prev_invstd[c] — so the previous
  * unit's backward skips its reduce pass. add2_mask (optional, needs add1 and add2): add2
  * enters as add2 * (add2_mask > 0) (a unit's identity-residual gradient dout*(out > 0),
- * formed here rather than written by the unit tail's BatchNorm backward). */
+ * formed here rather than written by the unit tail's BatchNorm backward).
+ * flags (ABI 24): SGCN_DXF_MASK_DX: dx is stored as dx * (x0 > 0) (exact +0 where x0 <= 0):
+ * when x0 is the previous unit's output and dx its complete gradient, that unit's backward
+ * receives the gradient with its ReLU mask applied and reads its output nowhere for the
+ * mask (y = NULL / relu = 0 / no add2_mask in its calls); dmask_part and prev_part are
+ * unchanged, with or without prev_part. SGCN_DXF_ADD2_PLANE (needs add2_mask, which stays a
+ * full tensor): add2 is (B*C), one value per plane. */
+#define SGCN_DXF_MASK_DX 1
+#define SGCN_DXF_ADD2_PLANE 2
 int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const float* add1,
                        const float* add2, const float* add2_mask, float* dx, float* dmask_part,
                        const float* prev_s, const float* prev_mean, const float* prev_invstd,
-                       float* prev_part, int B, int C, int T, int V, void* stream);
+                       float* prev_part, int B, int C, int T, int V, int flags, void* stream);
 
 /* dmask[u][c] (+)= (sum_b dmask_part[b][c][u]) * (1 - tanh(mask[u][c])^2). */
 int sgcn_mask_grad_finalize(const float* part, const float* mask, int B, int C, int V,
@@ -405,6 +427,12 @@ int sgcn_pool(const float* x, float* out, int N, int M, int C, long long P, void
  * 16-byte aligned. */
 int sgcn_pool_bwd(const float* dout, float* dx, int N, int M, int C, long long P,
                   void* stream);
+
+/* The plane values of sgcn_pool_bwd alone (ABI 24): dplane[(n*M + m)*C + c] = (dout[n][c] *
+ * (1/M)) * (1/P), the value every element of that plane of dx holds (same expression and
+ * rounding), for the dy_plane / SGCN_DXF_ADD2_PLANE forms above. */
+int sgcn_pool_bwd_planes(const float* dout, float* dplane, int N, int M, int C, long long P,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Optimizer (main.py:301-322, 414: torch.optim.SGD, dampening 0, not maximize)

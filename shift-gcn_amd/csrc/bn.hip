@@ -464,13 +464,16 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ r, const float* __restrict__ rmean,
     const float* __restrict__ rinvstd, const float* __restrict__ dyc, float2* __restrict__ part,
-    float2* __restrict__ rpart, int C, int T, int V) {
+    float2* __restrict__ rpart, int C, int T, int V, int dyp) {
   SGCN_CRIT_PRIO();
   __shared__ float s0[kThreads], s1[kThreads], red[2 * kThreads / 64];
   const int plane = blockIdx.x, c = plane % C;
   const int P = T * V;
   const size_t off = (size_t)plane * P;
   const int i = threadIdx.x;
+  // dyp: dy holds one value per plane (element o of the plane reads dy[plane])
+  const float* __restrict__ dyq = dyp ? dy + plane : dy + off;
+  const int dys = dyp ? 0 : 1;
   float rm = 0.f, ri = 0.f, d1 = 1.f, d2 = 0.f, d3 = 0.f;
   if (RESBN) { rm = rmean[c]; ri = rinvstd[c]; }
   if (DYT) { d1 = dyc[c]; d2 = dyc[C + c]; d3 = dyc[2 * C + c]; }
@@ -489,7 +492,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
           const int o = min(t0 + u * G, T - 1) * V + v;
-          gv[u] = dy[off + o];
+          gv[u] = dyq[o * dys];
           if (RELU) yv[u] = y[off + o];
           xv[u] = x[off + o + xd];
           if (RESBN) rv[u] = r[off + o];
@@ -523,7 +526,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_reduce_kernel(
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int o = min(base + u * kThreads + i, P - 1);
-        gv[u] = dy[off + o];
+        gv[u] = dyq[o * dys];
         if (RELU) yv[u] = y[off + o];
         xv[u] = x[off + o];
         if (RESBN) rv[u] = r[off + o];
@@ -557,7 +560,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_ja_kernel(
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ r, const float* __restrict__ rmean,
     const float* __restrict__ rinvstd, const float* __restrict__ dyc, float2* __restrict__ part,
-    float2* __restrict__ rpart, int C, int T, int V) {
+    float2* __restrict__ rpart, int C, int T, int V, int dyp) {
   SGCN_CRIT_PRIO();
   __shared__ float s0[NT], s1[NT], red[2 * NT / 64];
   const int plane = blockIdx.x, c = plane % C;
@@ -573,12 +576,18 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_ja_kernel(
   const unsigned xo = vo + (unsigned)((PER_JOINT ? vx - w : 0) * 4);
   float gv[LPT], yv[RELU ? LPT : 1], xv[LPT], rv[RESBN ? LPT : 1];
   {
-    const auto dyr = make_rsrc(dy + off, pb), xr = make_rsrc(x + off, pb);
+    const auto xr = make_rsrc(x + off, pb);
+    if (dyp) {   // one value per plane (a lane's elements past the plane are zeroed below)
+      const float pv = dy[plane];
 #pragma unroll
-    for (int e = 0; e < LPT; ++e) {
-      gv[e] = bload(dyr, vo + e * vstep, 0);
-      xv[e] = bload(xr, xo + e * vstep, 0);
+      for (int e = 0; e < LPT; ++e) gv[e] = pv;
+    } else {
+      const auto dyr = make_rsrc(dy + off, pb);
+#pragma unroll
+      for (int e = 0; e < LPT; ++e) gv[e] = bload(dyr, vo + e * vstep, 0);
     }
+#pragma unroll
+    for (int e = 0; e < LPT; ++e) xv[e] = bload(xr, xo + e * vstep, 0);
     if (RELU) {
       const auto yr = make_rsrc(y + off, pb);
 #pragma unroll
@@ -869,13 +878,14 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_ja_kernel(
 // same one-pass assignment (a thread owns destination joint v' and so source joint
 // u = (v' - c) mod V: one mask value, one dmask accumulator), with the whole plane's loads
 // in flight at once. dx is bit-identical; the plane sums only change order.
-template <int NT, int LPT, bool ADD1, bool ADD2, bool PART, bool A2M>
+template <int NT, int LPT, bool ADD1, bool ADD2, bool PART, int A2M>
 __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
     const float* __restrict__ dxt, const float* __restrict__ x0, const float* __restrict__ m,
     const float* __restrict__ add1, const float* __restrict__ add2, float* __restrict__ dx,
     float* __restrict__ dmask_part, const float* __restrict__ ps,
     const float* __restrict__ pmean, const float* __restrict__ pinvstd,
-    float2* __restrict__ bn_part, int C, int T, int V, const float* __restrict__ add2m) {
+    float2* __restrict__ bn_part, int C, int T, int V, const float* __restrict__ add2m,
+    int flags) {
   SGCN_CRIT_PRIO();
 #ifdef SGCN_DIAG_F1B_REAL
   return;   // timing diagnostic only: the pass is fused into the contraction (pwconv.hip)
@@ -893,7 +903,9 @@ __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
   const unsigned vo = own ? (unsigned)tid * 4u : 0x80000000u, vstep = (unsigned)NTJ * 4u;
   const unsigned pb = (unsigned)P * 4u;
   const unsigned uo = vo + (unsigned)((us - vd) * 4);
-  float gv[LPT], xq[LPT], a1[ADD1 ? LPT : 1], a2[ADD2 ? LPT : 1], a2q[A2M ? LPT : 1];
+  const bool mdx = flags & SGCN_DXF_MASK_DX;
+  constexpr bool A2P = A2M == 2;   // add2 holds one value per plane
+  float gv[LPT], xq[LPT], a1[ADD1 ? LPT : 1], a2[ADD2 && !A2P ? LPT : 1], a2q[A2M ? LPT : 1];
   float sv[PART ? LPT : 1];
   {
 #ifdef SGCN_DIAG_F1B_BOUND
@@ -914,7 +926,7 @@ __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
 #pragma unroll
       for (int e = 0; e < LPT; ++e) a1[e] = bload(ar, vo + e * vstep, 0);
     }
-    if (ADD2) {
+    if (ADD2 && !A2P) {
       const auto ar = make_rsrc(add2 + off, pb);
 #pragma unroll
       for (int e = 0; e < LPT; ++e) a2[e] = bload(ar, vo + e * vstep, 0);
@@ -931,16 +943,18 @@ __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
     }
   }
   const float mu = m[us * C + c];
-  float pm = 0.f, pi = 0.f;
+  float pm = 0.f, pi = 0.f, a2v = 0.f;
   if (PART) { pm = pmean[c]; pi = pinvstd[c]; }
+  if (A2P) a2v = add2[plane];   // (past the plane its mask a2q is 0)
   const auto dxr = make_rsrc(dx + off, pb);
   float acc = 0.f, b0 = 0.f, b1 = 0.f;
 #pragma unroll
   for (int e = 0; e < LPT; ++e) {
     float val = gv[e] * mu;
     if (ADD1) val += a1[e];
-    if (ADD2) val += A2M ? (a2q[e] > 0.f ? a2[e] : 0.f) : a2[e];
-    bstore(dxr, val, vo + e * vstep, 0);
+    if (ADD2) val += A2M ? (a2q[e] > 0.f ? (A2P ? a2v : a2[e]) : 0.f) : a2[e];
+    // mdx: dx leaves with the ReLU mask of x0 (the previous unit's output) already applied
+    bstore(dxr, (xq[e] > 0.f || !mdx) ? val : 0.f, vo + e * vstep, 0);
     acc = fmaf(gv[e], xq[e], acc);   // past the plane both loads are 0
     if (PART) {
       const float g = xq[e] > 0.f ? val : 0.f;   // x0 = 0 past the plane
@@ -1018,14 +1032,22 @@ __global__ __launch_bounds__(kThreads) void gcn_gather_kernel(const float* __res
 // A2M: add2 enters masked, add2 * (add2m > 0) — the identity-residual gradient of a
 // TCN_GCN_unit, g = dout * (out > 0), formed here instead of being written by the tail's
 // BatchNorm backward.
+// flags (wave-uniform, no instantiation of their own): SGCN_DXF_MASK_DX stores
+// dx * (x0 > 0), i.e. the previous unit's output gradient with its ReLU mask applied, so
+// none of that unit's backward kernels reads its output for the mask (the same
+// `x0 > 0 ? val : 0` PART sums; independent of PART). SGCN_DXF_ADD2_PLANE (the masked form
+// only; A2M = 2 in the plane-resident kernel, whose add2 load array it drops): add2 holds
+// one value per plane (the gradient of a global average pool).
 template <bool ADD1, bool ADD2, bool PART, bool A2M = false>
 __global__ __launch_bounds__(kThreads) void gcn_dx_finish_kernel(
     const float* __restrict__ dxt, const float* __restrict__ x0, const float* __restrict__ m,
     const float* __restrict__ add1, const float* __restrict__ add2, float* __restrict__ dx,
     float* __restrict__ dmask_part, const float* __restrict__ ps,
     const float* __restrict__ pmean, const float* __restrict__ pinvstd,
-    float2* __restrict__ bn_part, int C, int T, int V, const float* __restrict__ add2m) {
+    float2* __restrict__ bn_part, int C, int T, int V, const float* __restrict__ add2m,
+    int flags) {
   SGCN_CRIT_PRIO();
+  const bool mdx = flags & SGCN_DXF_MASK_DX, a2p = flags & SGCN_DXF_ADD2_PLANE;
   // One pass: thread i owns destination joint v' = i % V of rows t = i / V (mod G), so its
   // source joint u = (v' - c) mod V is fixed: one mask value, one dmask accumulator, and
   // the x0 factor of the mask gradient, x0[t, (u + c) mod V] = x0[t, v'], is the element
@@ -1052,7 +1074,7 @@ __global__ __launch_bounds__(kThreads) void gcn_dx_finish_kernel(
         gv[k] = dxt[off + row + us];
         xq[k] = x0[off + row + vd];
         if (ADD1) a1[k] = add1[off + row + vd];
-        if (ADD2) a2[k] = add2[off + row + vd];
+        if (ADD2) a2[k] = a2p ? add2[plane] : add2[off + row + vd];
         if (A2M) a2q[k] = add2m[off + row + vd];
         if (PART) sv[k] = ps[off + row + vd];
       }
@@ -1062,7 +1084,7 @@ __global__ __launch_bounds__(kThreads) void gcn_dx_finish_kernel(
         float val = gv[k] * mu;
         if (ADD1) val += a1[k];
         if (ADD2) val += A2M ? (a2q[k] > 0.f ? a2[k] : 0.f) : a2[k];
-        if (t < T) dx[off + t * V + vd] = val;
+        if (t < T) dx[off + t * V + vd] = (xq[k] > 0.f || !mdx) ? val : 0.f;
         acc += (t < T) ? gv[k] * xq[k] : 0.f;
         if (PART) {
           const float g = (t < T && xq[k] > 0.f) ? val : 0.f;
@@ -1343,9 +1365,10 @@ int sgcn_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* x
                        const float* mean, const float* invstd, int per_joint, const float* r,
                        const float* rmean,
                        const float* rinvstd, const float* dy_coef, float* part, float* rpart,
-                       int B, int C, int T, int V, void* stream) {
+                       int B, int C, int T, int V, int dy_plane, void* stream) {
   SGCN_PLANE_CHECK();
   SGCN_REQUIRE(B > 0 && T > 0 && dy && x && mean && invstd && part && (y || !relu));
+  const int dyp = dy_plane != 0;
   SGCN_REQUIRE(!dy_coef || (y && relu));
   SGCN_REQUIRE((r == nullptr) == (rpart == nullptr) && (!r || (rmean && rinvstd)));
   SGCN_REQUIRE(per_joint == 0 || per_joint == 3);
@@ -1360,10 +1383,10 @@ int sgcn_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* x
 #define SGCN_RJ(NT, L, PJ, RL, RB)                                                             \
   (dy_coef ? bn_bwd_reduce_ja_kernel<NT, L, PJ, RL, RB, true><<<g, NT, 0, st>>>(                \
                  dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,            \
-                 (float2*)rpart, C, T, V)                                                      \
+                 (float2*)rpart, C, T, V, dyp)                                                 \
            : bn_bwd_reduce_ja_kernel<NT, L, PJ, RL, RB, false><<<g, NT, 0, st>>>(               \
                  dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,            \
-                 (float2*)rpart, C, T, V))
+                 (float2*)rpart, C, T, V, dyp))
 #define SGCN_RJ_L(NT, PJ, RL, RB)                                                              \
   do {                                                                                         \
     if (lpt == 8) SGCN_RJ(NT, 8, PJ, RL, RB); else if (lpt == 16) SGCN_RJ(NT, 16, PJ, RL, RB); \
@@ -1385,10 +1408,10 @@ int sgcn_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* x
 #define SGCN_RED(PJ, RL, RB)                                                                \
   (dy_coef ? bn_bwd_reduce_kernel<PJ, RL, RB, true><<<g, kThreads, 0, st>>>(                   \
                  dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,           \
-                 (float2*)rpart, C, T, V)                                                     \
+                 (float2*)rpart, C, T, V, dyp)                                                \
            : bn_bwd_reduce_kernel<PJ, RL, RB, false><<<g, kThreads, 0, st>>>(                  \
                  dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,           \
-                 (float2*)rpart, C, T, V))
+                 (float2*)rpart, C, T, V, dyp))
   if (per_joint == 3) {   // x = the pre-shift_out contraction output (see the kernel)
     if (rb) SGCN_RED(true, true, true); else SGCN_RED(true, true, false);
   } else {
@@ -1557,10 +1580,12 @@ int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const 
                        const float* add2, const float* add2_mask, float* dx, float* dmask_part,
                        const float* prev_s, const float* prev_mean, const float* prev_invstd,
                        float* prev_part, int B,
-                       int C, int T, int V, void* stream) {
+                       int C, int T, int V, int flags, void* stream) {
   SGCN_PLANE_CHECK();
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(dxt && x0 && m && dx && dmask_part);
+  SGCN_REQUIRE((flags & ~(SGCN_DXF_MASK_DX | SGCN_DXF_ADD2_PLANE)) == 0);
+  SGCN_REQUIRE(!(flags & SGCN_DXF_ADD2_PLANE) || add2_mask);   // the masked (identity-unit) form
   SGCN_REQUIRE(!prev_part || (prev_s && prev_mean && prev_invstd));
   SGCN_REQUIRE(!add2_mask || add2);
   hipStream_t st = (hipStream_t)stream;
@@ -1575,7 +1600,7 @@ int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const 
 #define SGCN_FJ(NT, L, A1, A2, PT, AM)                                                         \
   gcn_dx_finish_ja_kernel<NT, L, A1, A2, PT, AM><<<B * C, NT, 0, st>>>(                        \
       dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,     \
-      add2_mask)
+      add2_mask, flags)
 #define SGCN_FJ_L(NT, A1, A2, PT, AM)                                                          \
   do {                                                                                         \
     if (lpt == 8) SGCN_FJ(NT, 8, A1, A2, PT, AM);                                              \
@@ -1587,9 +1612,9 @@ int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const 
   do { if (nt == kThreads) SGCN_FJ_L(kThreads, A1, A2, PT, AM); else SGCN_FJ_L(512, A1, A2, PT, AM); } while (0)
 #define SGCN_FJ_P(A1, A2, AM)                                                                  \
   do { if (pp) SGCN_FJ_T(A1, A2, true, AM); else SGCN_FJ_T(A1, A2, false, AM); } while (0)
-      if (add2_mask) SGCN_FJ_P(true, true, true);
-      else if (add1) { if (add2) SGCN_FJ_P(true, true, false); else SGCN_FJ_P(true, false, false); }
-      else { if (add2) SGCN_FJ_P(false, true, false); else SGCN_FJ_P(false, false, false); }
+      if (add2_mask) { if (flags & SGCN_DXF_ADD2_PLANE) SGCN_FJ_P(true, true, 2); else SGCN_FJ_P(true, true, 1); }
+      else if (add1) { if (add2) SGCN_FJ_P(true, true, 0); else SGCN_FJ_P(true, false, 0); }
+      else { if (add2) SGCN_FJ_P(false, true, 0); else SGCN_FJ_P(false, false, 0); }
 #undef SGCN_FJ_P
 #undef SGCN_FJ_T
 #undef SGCN_FJ_L
@@ -1602,18 +1627,18 @@ int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const 
     if (pp)
       gcn_dx_finish_kernel<true, true, true, true><<<B * C, kThreads, 0, st>>>(
           dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
-          add2_mask);
+          add2_mask, flags);
     else
       gcn_dx_finish_kernel<true, true, false, true><<<B * C, kThreads, 0, st>>>(
           dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
-          add2_mask);
+          add2_mask, flags);
     SGCN_LAUNCH_CHECK();
     return 0;
   }
 #define SGCN_FIN(A1, A2, PT)                                                                \
   gcn_dx_finish_kernel<A1, A2, PT><<<B * C, kThreads, 0, st>>>(                           \
       dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,  \
-      nullptr)
+      nullptr, flags)
 #define SGCN_FIN_P(A1, A2)                                                                  \
   do {                                                                                      \
     if (pp) SGCN_FIN(A1, A2, true);                                                         \

@@ -220,6 +220,21 @@ __global__ __launch_bounds__(kHT) void pool_bwd_kernel(const float* __restrict__
   }
 }
 
+// The plane values of pool_bwd_kernel alone: dplane[(n*M + m)*C + c] = (dout[n][c] * (1/M))
+// * (1/P), the one value every element of that plane of dx holds (same expression and
+// rounding), for consumers that take a per-plane gradient instead of the expanded tensor.
+__global__ __launch_bounds__(kHT) void pool_bwd_planes_kernel(const float* __restrict__ dout,
+                                                              float* __restrict__ dplane,
+                                                              long long rows, int C, int M,
+                                                              long long P) {
+  const long long row = (long long)blockIdx.x * kHT + threadIdx.x;   // (n*M + m)*C + c
+  if (row >= rows) return;
+  const float rm = 1.f / (float)M, rp = 1.f / (float)P;
+  const int c = (int)(row % C);
+  const long long n = row / C / M;
+  dplane[row] = (dout[n * C + c] * rm) * rp;
+}
+
 unsigned grid1(long long total) { return (unsigned)((total + kHT - 1) / kHT); }
 
 }  // namespace
@@ -301,6 +316,18 @@ int sgcn_pool_bwd(const float* dout, float* dx, int N, int M, int C, long long P
   SGCN_REQUIRE(total < (1ll << 40));
   pool_bwd_kernel<<<grid1((total + 3) / 4), kHT, 0, (hipStream_t)stream>>>(dout, dx, total, C,
                                                                            M, P);
+  SGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+int sgcn_pool_bwd_planes(const float* dout, float* dplane, int N, int M, int C, long long P,
+                         void* stream) {
+  SGCN_REQUIRE(N >= 0 && M > 0 && C > 0 && P > 0);
+  const long long rows = (long long)N * M * C;
+  if (rows == 0) return 0;
+  SGCN_REQUIRE(dout && dplane && rows < (1ll << 31));
+  pool_bwd_planes_kernel<<<grid1(rows), kHT, 0, (hipStream_t)stream>>>(dout, dplane, rows, C, M,
+                                                                       P);
   SGCN_LAUNCH_CHECK();
   return 0;
 }

@@ -912,7 +912,9 @@ __global__ __launch_bounds__(NT) void tshift_bwd_s2_kernel(
 // follows this shift (Shift_tcn.bn2 inside a TCN_GCN_unit, shift_gcn.py:73,161-162),
 // formed while staging: gout = k1*(gy > 0 ? gdy : 0) + k2*gx + k3 (gdy = the unit's output
 // gradient, gy = its output, gx = bn2's input S, k = sgcn_bn_bwd_finalize coefficients),
-// so that gradient tensor is never written.
+// so that gradient tensor is never written. GP = 2: gdy already carries the ReLU mask (the
+// producer stored dout * (out > 0), sgcn_gcn_dx_finish SGCN_DXF_MASK_DX), gout = k1*gdy +
+// k2*gx + k3 and gy is not loaded. gdyp (wave-uniform): gdy holds one value per plane.
 //
 // GBN (with AFFINE + BNP: Shift_tcn's shift_in inside a TCN_GCN_unit whose
 // Shift_gcn has no down conv): also the backward partials of Shift_gcn.bn, the per-joint
@@ -929,7 +931,7 @@ __global__ __launch_bounds__(NT) void tshift_bwd_s2_kernel(
 // H > 0, dh = (d - d_mean[c]) * d_invstd[c], to gdpart[j][plane] — the same six-sum form,
 // finalized by sgcn_bn_bwd_finalize_gbn with V = 1 — so no sgcn_bn_bwd_reduce pass over
 // (dA, H, Z, d) remains for the units with a down conv either.
-template <int NT, int LPT, bool AFFINE, bool RELU_MASK, bool BNP, bool GP, bool GBN,
+template <int NT, int LPT, bool AFFINE, bool RELU_MASK, bool BNP, int GP, bool GBN,
           bool GBD = false>
 __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
     const float* __restrict__ gout, const float* __restrict__ in,
@@ -942,7 +944,7 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
     const float* __restrict__ gz, const float* __restrict__ gzm,
     const float* __restrict__ gzi, float* __restrict__ gzpart, const float* __restrict__ gd = nullptr,
     const float* __restrict__ gdm = nullptr, const float* __restrict__ gdi = nullptr,
-    float* __restrict__ gdpart = nullptr) {
+    float* __restrict__ gdpart = nullptr, int gdyp = 0) {
   SGCN_CRIT_PRIO();
   static_assert(!GBN || (AFFINE && BNP && !GP), "GBN: shift_in with BNP");
   static_assert(!GBD || GBN, "GBD extends GBN");
@@ -972,22 +974,35 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
   {   // every global load of the plane in flight together
     const auto inr = make_rsrc(in + poff, nbytes);
     if (GP) {
-      const auto dyr = make_rsrc(gdy + poff, nbytes);
-      const auto yr = make_rsrc(gy + poff, nbytes);
       const auto xr = make_rsrc(gx + poff, nbytes);
-      float u1[LPT], u2[LPT];
+      float u1[GP == 1 ? LPT : 1], u2[LPT];
+      if (gdyp) {   // one value per plane (elements past the plane never reach the LDS plane)
+        const float pv = gdy[plane];
+#pragma unroll
+        for (int e = 0; e < LPT; ++e) t[e] = pv;
+      } else {
+        const auto dyr = make_rsrc(gdy + poff, nbytes);
+#pragma unroll
+        for (int e = 0; e < LPT; ++e) t[e] = bload(dyr, vo + e * vstep, 0);
+      }
+      if (GP == 1) {
+        const auto yr = make_rsrc(gy + poff, nbytes);
+#pragma unroll
+        for (int e = 0; e < LPT; ++e) u1[e] = bload(yr, vo + e * vstep, 0);
+      }
 #pragma unroll
       for (int e = 0; e < LPT; ++e) {
         const unsigned vb = vo + e * vstep;
-        t[e] = bload(dyr, vb, 0);
-        u1[e] = bload(yr, vb, 0);
         u2[e] = bload(xr, vb, 0);
         rin_r[e] = bload(inr, vb, 0);
       }
       // bn2's backward coefficients, read while the plane's loads fly
       const float k1 = gcoef[c], k2 = gcoef[C + c], k3 = gcoef[2 * C + c];
 #pragma unroll
-      for (int e = 0; e < LPT; ++e) t[e] = k1 * (u1[e] > 0.f ? t[e] : 0.f) + k2 * u2[e] + k3;
+      for (int e = 0; e < LPT; ++e) {
+        const float gm = GP == 1 ? (u1[e] > 0.f ? t[e] : 0.f) : t[e];
+        t[e] = k1 * gm + k2 * u2[e] + k3;
+      }
     } else {
       const auto gr = make_rsrc(gout + poff, gbytes);
 #pragma unroll
@@ -1438,21 +1453,21 @@ constexpr size_t kRaLdsMax = 65536;
 
 // launch tshift_bwd_ra_kernel on nt threads (256 or 512) with LPT = ra_lpt(H*W, nt, W);
 // returns false (nothing launched) when the plane does not fit its LDS or registers
-template <bool AFFINE, bool RELU, bool BNP, bool GP, bool GBN, bool GBD = false>
+template <bool AFFINE, bool RELU, bool BNP, int GP, bool GBN, bool GBD = false>
 bool launch_ra(int nt, const float* gout, const float* in, const float* xpos,
                const float* ypos, const float* scale, const float* shift, const float* bmu,
                const float* bis, float* gin, float2* pg, float2* bp, int B, int C, int H,
                int W, const float* gdy, const float* gy, const float* gx, const float* gcoef,
                const float* gz, const float* gzm, const float* gzi, float* gzpart,
                hipStream_t st, const float* gd = nullptr, const float* gdm = nullptr,
-               const float* gdi = nullptr, float* gdpart = nullptr) {
+               const float* gdi = nullptr, float* gdpart = nullptr, int gdyp = 0) {
   const int lpt = ra_lpt(H * W, nt, W);
   const size_t lds = ra_lds_bytes(H, W, nt, GBN);
   if (lpt == 0 || lds > kRaLdsMax) return false;
 #define SGCN_RA(NT, L)                                                                         \
   tshift_bwd_ra_kernel<NT, L, AFFINE, RELU, BNP, GP, GBN, GBD><<<B * C, NT, lds, st>>>(        \
       gout, in, xpos, ypos, scale, shift, bmu, bis, gin, pg, bp, C, H, W, gdy, gy, gx, gcoef,  \
-      gz, gzm, gzi, gzpart, gd, gdm, gdi, gdpart)
+      gz, gzm, gzi, gzpart, gd, gdm, gdi, gdpart, gdyp)
   if (nt == 256) {
     if (lpt == 8) SGCN_RA(256, 8); else if (lpt == 16) SGCN_RA(256, 16); else if (lpt == 24) SGCN_RA(256, 24); else SGCN_RA(256, 32);
   } else {
@@ -1653,10 +1668,10 @@ int sgcn_tshift_fwd_tail(const float* in, float* out, const float* xpos, const f
 int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const float* coef,
                          const float* in, const float* xpos, const float* ypos, float* gin,
                          float* gx, float* gy, void* ws, size_t ws_bytes, int B, int C, int H,
-                         int W, int ypos_is_raw, void* stream) {
+                         int W, int ypos_is_raw, int dy_plane, void* stream) {
   SGCN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0);
   SGCN_REQUIRE(H * W <= kBwdLdsMax);   // LDS-staged stride-1 planes only (caller falls back)
-  SGCN_REQUIRE(dy && y && s && coef && in && xpos && ypos && gin && ws);
+  SGCN_REQUIRE(dy && s && coef && in && xpos && ypos && gin && ws);
   SGCN_REQUIRE((gx == nullptr) == (gy == nullptr));
   SGCN_REQUIRE(ws_bytes >= sgcn_tshift_bwd_ws_bytes(B, C));
   SGCN_REQUIRE((long long)B * C < (1LL << 31));
@@ -1666,9 +1681,17 @@ int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const 
   // 512 threads above 4K-float planes: 256 threads at NTU T = 300 measured 0.3 % slower per
   // step (profiles/r03_x1b/ab_x1b_bound.txt, variant bnin256)
   const int ntb = H * W <= 4096 ? 256 : 512;
-  const bool ok = launch_ra<false, true, false, true, false>(
-      ntb, nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr, B, C,
-      H, W, dy, y, s, coef, nullptr, nullptr, nullptr, nullptr, st);
+  const int dyp = dy_plane != 0;
+  // y == NULL: dy already carries the ReLU mask (GP = 2: the y plane is not loaded)
+  const bool ok =
+      y ? launch_ra<false, true, false, 1, false>(
+              ntb, nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr,
+              B, C, H, W, dy, y, s, coef, nullptr, nullptr, nullptr, nullptr, st, nullptr,
+              nullptr, nullptr, nullptr, dyp)
+        : launch_ra<false, true, false, 2, false>(
+              ntb, nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr,
+              B, C, H, W, dy, nullptr, s, coef, nullptr, nullptr, nullptr, nullptr, st, nullptr,
+              nullptr, nullptr, nullptr, dyp);
   SGCN_REQUIRE(ok);   // W <= 64, <= 32 elements per thread, padded plane <= 64 KiB (ops.ra_fits)
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 # same-box A/B of two builds (tuning only, e.g. tools/ab_lib.sh): another in-tree build of
 # the same ABI
 LIB_PATH = os.environ.get("SGCN_LIB_PATH", LIB_PATH)
-ABI_VERSION = 23
+ABI_VERSION = 24
 BATCH_MAX = 32            # include/shiftgcn.h SGCN_BATCH_MAX
 ABI_DIAG_FLAG = 0x10000   # include/shiftgcn.h SGCN_ABI_DIAG_FLAG: a diagnostic build
 EINVAL = -22
@@ -64,16 +64,16 @@ SIGNATURES = {
     "sgcn_bn_apply": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I,
                            _P]),
     "sgcn_bn_bwd_reduce": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I,
-                                _I, _P]),
+                                _I, _I, _P]),
     "sgcn_bn_bwd_finalize": (_I, [_P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "sgcn_bn_bwd_apply": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                                _P]),
     "sgcn_mask_prep": (_I, [_P, _P, _I, _P]),
     "sgcn_gcn_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "sgcn_gcn_dx_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
-                                _P]),
+                                _I, _P]),
     "sgcn_tshift_bwd_bnin": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _I, _I,
-                                  _I, _I, _P]),
+                                  _I, _I, _I, _P]),
     "sgcn_mask_grad_finalize": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "sgcn_modalities": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sgcn_tshift_bwd_gbn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
@@ -87,6 +87,7 @@ SIGNATURES = {
     "sgcn_head_bwd_apply": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "sgcn_pool": (_I, [_P, _P, _I, _I, _I, _L, _P]),
     "sgcn_pool_bwd": (_I, [_P, _P, _I, _I, _I, _L, _P]),
+    "sgcn_pool_bwd_planes": (_I, [_P, _P, _I, _I, _I, _L, _P]),
     "sgcn_tshift_pos_finalize_many": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "sgcn_mask_prep_many": (_I, [_P, _P, _P, _I, _P]),
     "sgcn_mask_grad_finalize_many": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),

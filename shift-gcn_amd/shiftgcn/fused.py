@@ -316,14 +316,16 @@ def prepare_masks(gcns):
 
 
 def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, extra_out=None,
-                 pre6=None, off=False):
+                 pre6=None, off=False, mask_dx=False):
     """Returns (dx0, {param_name: grad}). With ``dy_coef`` ([3, Cout]) the incoming
     gradient is dH = k1*dH_arg + k2*H + k3 (Shift_tcn.bn's input gradient), evaluated
     on the fly by the BN-backward kernels instead of being materialised. ``pre6`` =
     (six-sum partials, Shift_tcn.bn stats) from sgcn_tshift_bwd_gbn: bn's backward
     partials were made by the shift_in backward launch (no reduce pass here). ``off``:
-    the weight-gradient launches go to the side stream (see _OffPath)."""
+    the weight-gradient launches go to the side stream (see _OffPath). ``mask_dx``: dx0 is
+    returned as dx0 * (x0 > 0) (only without a down conv, whose dx is accumulated after)."""
     x0 = s.x0
+    assert not (mask_dx and mod.has_down)
     B, Cin, T, V = x0.shape
     Cout = mod.out_channels
     g = {}
@@ -372,9 +374,10 @@ def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, e
     if prev is not None:   # also the previous unit's bn2 backward partials (x0 = its out)
         dx, mpart, extra_out["prev_part"] = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id,
                                                               add2=a2, prev=prev,
-                                                              add2_mask=a2m)
+                                                              add2_mask=a2m, mask_dx=mask_dx)
     else:
-        dx, mpart = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id, add2=a2, add2_mask=a2m)
+        dx, mpart = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id, add2=a2, add2_mask=a2m,
+                                      mask_dx=mask_dx)
     dmask = ops.grad_like(mod.Feature_Mask)
     fm = mod.Feature_Mask
     if BATCH_SIDE and (off or _defer_ok((fm,))):
@@ -611,7 +614,7 @@ def convbn_dx_and_dw(mod, s: ConvBnSaved, dRc, dx, accumulate, off=False):
 # TCN_GCN_unit
 # ======================================================================================
 class UnitSaved:
-    __slots__ = ("x", "gs", "ts", "rs", "out", "prev", "off")
+    __slots__ = ("x", "gs", "ts", "rs", "out", "prev", "off", "pm")
 
 
 def unit_forward(unit, x, training):
@@ -642,6 +645,12 @@ def unit_forward(unit, x, training):
     # operand for ops.gcn_dx_finish, that unit)
     prev = unit.__dict__.pop("_prev_tail", None)
     prev = prev[1:] if prev is not None and prev[0] is x else None
+    # the previous linked unit, when x is its output and this unit's gcn_dx_finish forms x's
+    # COMPLETE gradient (no residual conv, no gcn down conv: their dx is added after): that
+    # launch may store the gradient with x's ReLU mask applied (see _unit_backward)
+    pm = unit.__dict__.pop("_prev_out", None)
+    pm = pm[1] if (pm is not None and pm[0] is x and unit.residual_kind != "conv" and
+                   not unit.gcn1.has_down) else None
     # linked chains only; not while a hipGraph is being captured (the graph replays one
     # stream's launches in order)
     off = (ASYNC_DW and bool(unit.__dict__.get("_off_path")) and
@@ -687,9 +696,11 @@ def unit_forward(unit, x, training):
     if (nxt is not None and unit.residual_kind != "conv" and nxt.residual_kind != "conv"
             and not nxt.gcn1.has_down):
         nxt.__dict__["_prev_tail"] = (out, (S, sst), unit)
+    if nxt is not None:
+        nxt.__dict__["_prev_out"] = (out, unit)
     s = UnitSaved()
     s.x, s.gs, s.ts, s.rs, s.out, s.prev = x, gs, ts, rs, out, prev
-    s.off = off
+    s.off, s.pm = off, pm
     return out, s
 
 
@@ -718,21 +729,56 @@ def unit_backward(unit, s: UnitSaved, dout):
     return _unit_backward(unit, s, dout, _off_path_ok(unit, s))
 
 
+def _premask_ok(unit, x, off):
+    """Whether this unit may return its input gradient with the ReLU mask of ``x`` (the
+    previous linked unit's output) already applied: only if nothing but that unit's backward
+    sees the gradient. Not with tensor hooks or ``retain_grad`` on x, not when this backward
+    will not run that unit's node, not under ``torch.autograd.grad`` /
+    ``backward(inputs=...)`` (which may capture x's gradient: told from this unit's own
+    parameters, whose AccumulateGrad a plain backward runs, the query _defer_ok makes; a unit
+    without trainable parameters cannot tell and does not mask), ``create_graph`` or a
+    hipGraph capture."""
+    if not PREMASK or torch.cuda.is_current_stream_capturing():
+        return False
+    if getattr(x, "_backward_hooks", None) or x.retains_grad or x.grad_fn is None:
+        return False
+    if not off:   # (off: _off_path_ok has asked _defer_ok about every parameter)
+        params = [p for p in unit.parameters() if p.requires_grad]
+        if not params or not _defer_ok(params):
+            return False
+    try:
+        return bool(torch._C._will_engine_execute_node(x.grad_fn))
+    except RuntimeError:
+        return False
+
+
 def _unit_backward(unit, s: UnitSaved, dout, off):
+    """``dout``: the unit's output gradient, (B, C, To, V), or (B, C) = one value per plane
+    (_BlockFunction.backward; first branch below only)."""
     ts = s.ts
     S = ts.S
     so = unit.tcn1.shift_out
     B, Cout, To, V = S.shape
     kind = unit.residual_kind
     g = {}
+    # the next unit's gcn_dx_finish stored dout with this unit's ReLU mask applied
+    # (dout * (out > 0): exactly what every consumer below forms from (dout, out)), so no
+    # kernel of this backward reads ``out``. Told by identity: a gradient autograd summed
+    # with another contribution is a different tensor and takes the unmasked forms (also
+    # correct on a masked tensor: masking is idempotent)
+    pmk = unit.__dict__.pop("_premasked", None)
+    masked = pmk is not None and pmk is dout
+    y, relu = (None, False) if masked else (s.out, True)
+    # this unit masks for the previous one
+    mask_dx = s.pm is not None and _premask_ok(unit, s.x, off)
     cached = unit.__dict__.pop("_bwd_part", None)
     if cached is not None and cached[0] is dout and kind != "conv":
         part, rpart = cached[1], None   # made by the next unit's gcn_dx_finish
     elif kind == "conv":
-        part, rpart = ops.bn_bwd_reduce(dout, s.out, True, S, ts.sst, False, r=s.rs.Rc,
+        part, rpart = ops.bn_bwd_reduce(dout, y, relu, S, ts.sst, False, r=s.rs.Rc,
                                         rst=s.rs.rst)
     else:
-        part, rpart = ops.bn_bwd_reduce(dout, s.out, True, S, ts.sst, False)
+        part, rpart = ops.bn_bwd_reduce(dout, y, relu, S, ts.sst, False)
     coef2, g["tcn1.bn2.weight"], g["tcn1.bn2.bias"] = ops.bn_bwd_finalize(
         part, B, Cout, B * To * V, ts.sst, unit.tcn1.bn2)
     if kind != "conv" and so.stride == 1 and ops.ra_fits(To * V, V):
@@ -740,16 +786,18 @@ def _unit_backward(unit, s: UnitSaved, dout, off):
         # forms dS while staging, gcn_dx_finish forms dout*(out > 0)
         fo = {}
         (dA, coefA), gt = tcn_core_backward(unit.tcn1, ts, None, materialize_dx=False,
-                                            gpre=(dout, s.out, coef2), gcn_z=_gcn_z(unit, s),
+                                            gpre=(dout, y, coef2), gcn_z=_gcn_z(unit, s),
                                             out=fo, off=off)
         g.update({"tcn1." + k: v for k, v in gt.items()})
         extra = {}
         dx, gg = gcn_backward(unit.gcn1, s.gs, dA,
-                              extra_dx=(dout, s.out) if kind == "identity" else None,
+                              extra_dx=(dout, y) if kind == "identity" else None,
                               dy_coef=coefA, prev=None if s.prev is None else s.prev[0],
-                              extra_out=extra, pre6=fo.get("pre6"), off=off)
+                              extra_out=extra, pre6=fo.get("pre6"), off=off, mask_dx=mask_dx)
         if s.prev is not None:
             s.prev[1].__dict__["_bwd_part"] = (dx, extra["prev_part"])
+        if mask_dx:
+            s.pm.__dict__["_premasked"] = dx
         g.update({"gcn1." + k: v for k, v in gg.items()})
         return dx, g
     dS = torch.empty_like(S)
@@ -758,13 +806,13 @@ def _unit_backward(unit, s: UnitSaved, dout, off):
         coefR, g["residual.bn.weight"], g["residual.bn.bias"] = ops.bn_bwd_finalize(
             rpart, B, Cout, B * To * V, s.rs.rst, unit.residual.bn)
         dres = torch.empty_like(s.rs.Rc)
-        ops.bn_bwd_apply(dout, s.out, True, S, coef2, False, r=s.rs.Rc, rcoef=coefR, dr=dres,
+        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, r=s.rs.Rc, rcoef=coefR, dr=dres,
                          dx=dS)
     elif kind == "identity":
         dres = torch.empty_like(s.x)
-        ops.bn_bwd_apply(dout, s.out, True, S, coef2, False, dr=dres, dx=dS)
+        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, dr=dres, dx=dS)
     else:
-        ops.bn_bwd_apply(dout, s.out, True, S, coef2, False, dx=dS)
+        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, dx=dS)
     fo = {}
     (dA, coefA), gt = tcn_core_backward(unit.tcn1, ts, dS, materialize_dx=False,
                                         gcn_z=_gcn_z(unit, s), out=fo, off=off)
@@ -772,9 +820,11 @@ def _unit_backward(unit, s: UnitSaved, dout, off):
     extra = {}
     dx, gg = gcn_backward(unit.gcn1, s.gs, dA, extra_dx=dres if kind == "identity" else None,
                           dy_coef=coefA, prev=None if s.prev is None else s.prev[0],
-                          extra_out=extra, pre6=fo.get("pre6"), off=off)
+                          extra_out=extra, pre6=fo.get("pre6"), off=off, mask_dx=mask_dx)
     if s.prev is not None:   # kind != "conv" and no gcn down conv: dx is final here
         s.prev[1].__dict__["_bwd_part"] = (dx, extra["prev_part"])
+    if mask_dx:
+        s.pm.__dict__["_premasked"] = dx
     g.update({"gcn1." + k: v for k, v in gg.items()})
     if kind == "conv":
         gr = convbn_dx_and_dw(unit.residual, s.rs, dres, dx, accumulate=True, off=off)
@@ -812,6 +862,12 @@ GBN_FUSION = int(os.environ.get("SGCN_GBN_FUSION", "2"))
 # gradient finalizes, the next unit's mask and the forward's down / residual conv branches.
 # SGCN_ASYNC_DW=0 serializes everything (bench.py's roofline steps, A/B).
 ASYNC_DW = int(os.environ.get("SGCN_ASYNC_DW", "1"))
+# A linked unit's output gradient arrives with its ReLU mask already applied (stored by the
+# next unit's gcn_dx_finish, which reads that output anyway), and the pool's gradient as one
+# value per plane, so no backward kernel reads a unit's output only for `out > 0` and the
+# pool's expanded gradient is never written (_unit_backward, _plane_dy). Bit-identical.
+# A/B knob: 0 = every consumer re-reads the output for its mask, as before.
+PREMASK = int(os.environ.get("SGCN_PREMASK", "1"))
 
 
 def trainable(module):
@@ -851,7 +907,8 @@ class _BlockFunction(torch.autograd.Function):
                 "called a second time; its saved activations are released after the first "
                 "backward (retain_graph=True / double backward is not supported)")
         _, bwd = ctx.impl
-        dx, grads = bwd(ctx.module, ctx.saved, dy.contiguous())
+        dyp = _plane_dy(ctx, dy)
+        dx, grads = bwd(ctx.module, ctx.saved, dy.contiguous() if dyp is None else dyp)
         ctx.saved = None
         out = []
         for n, p in zip(ctx.names, ctx.params):
@@ -861,6 +918,22 @@ class _BlockFunction(torch.autograd.Function):
                 g = None
             out.append(g)
         return (None, None, dx) + tuple(out)
+
+
+def _plane_dy(ctx, dy):
+    """The (B, C) plane values of an output gradient expanded over (T, V) (both strides 0:
+    the pool's backward, ``unit(x).mean().backward()``), when the unit's backward takes them
+    in place of the materialised tensor (the fused branch of _unit_backward: no residual
+    conv, stride 1, ra_fits); else None."""
+    if not (PREMASK and ctx.impl is UNIT_IMPL and dy.dim() == 4 and dy.stride(2) == 0 and
+            dy.stride(3) == 0 and isinstance(ctx.saved, UnitSaved)):
+        return None
+    unit = ctx.module
+    To, V = dy.shape[2], dy.shape[3]
+    if (unit.residual_kind == "conv" or unit.tcn1.shift_out.stride != 1 or
+            not ops.ra_fits(To * V, V)):
+        return None
+    return dy[:, :, 0, 0].contiguous()
 
 
 class _InferFlag(threading.local):

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import torch
 
-from . import ops
+from . import fused, ops
 
 
 def _batch_stats(bn) -> bool:
@@ -63,6 +63,12 @@ class _PoolFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if fused.PREMASK:
+            # every (T, V) plane of the gradient holds one value: only those are written,
+            # expanded with stride 0 (the last unit's backward takes them per plane; any
+            # other consumer sees an ordinary expanded gradient, like torch's own mean)
+            dp = ops.pool_bwd(g.contiguous(), ctx.shape, ctx.N, ctx.M, planes=True)
+            return dp[:, :, None, None].expand(ctx.shape), None, None
         return ops.pool_bwd(g.contiguous(), ctx.shape, ctx.N, ctx.M), None, None
 
 

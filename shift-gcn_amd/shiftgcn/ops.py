@@ -500,24 +500,40 @@ def tshift_bwd_gbn(gout, inp, xpos, ypos, st: "BnStats", z, zst: "BnStats", defe
 BNIN_MAX_PLANE = 16384   # sgcn_tshift_bwd_bnin: LDS-staged stride-1 planes only
 
 
+def _plane_dy(dy, x):
+    """Whether ``dy`` is a per-plane gradient of ``x`` (B, C, T, V): a (B, C) tensor, one
+    value per plane, instead of x's shape."""
+    if dy.dim() == 2:
+        if tuple(dy.shape) != tuple(x.shape[:2]):
+            raise ValueError(f"per-plane gradient {tuple(dy.shape)} of planes {tuple(x.shape)}")
+        return True
+    return False
+
+
 def tshift_bwd_bnin(dy, y, s, coef, inp, xpos, ypos, defer_pos=False, pos_out=None):
     """Stride-1 shift backward (ReLU mask on ``inp``) whose output gradient is the input
     gradient of the following BatchNorm, k1*(y > 0 ? dy : 0) + k2*s + k3 (s = that
-    BatchNorm's input), formed in the kernel. Returns (grad_input, grad_xpos, grad_ypos)."""
+    BatchNorm's input), formed in the kernel. ``y`` None: ``dy`` already carries the mask
+    (k1*dy + k2*s + k3; no y plane is read). ``dy`` (B, C): one value per plane. Returns
+    (grad_input, grad_xpos, grad_ypos)."""
     for t, n in ((dy, "dy"), (y, "y"), (s, "s"), (inp, "input"), (coef, "coef")):
-        check_input(t, n)
+        if t is not None:
+            check_input(t, n)
     B, C, H, W = inp.shape
+    dyp = _plane_dy(dy, inp)
     lib = _lib.load()
     dev = inp.device
     gin = torch.empty_like(inp)
     nbytes = lib.sgcn_tshift_bwd_ws_bytes(B, C)
     ws = torch.empty((max(nbytes, 4) + 3) // 4, device=dev, dtype=_F32)
     gx, gy, pp = _pos_out(defer_pos, ws, B, C, dev, pos_out)
-    nb = 4 * (3 * dy.numel() + 2 * inp.numel())
+    # reads: dy (a full tensor or B*C values), y (unless dy is pre-masked), s, inp; write gin
+    nb = 4 * (dy.numel() + (2 + (y is not None)) * s.numel() + inp.numel())
     with _timed("tshift_bwd", 0, nb, inp, _shp(inp)):
         rc = lib.sgcn_tshift_bwd_bnin(
             _ptr(dy), _ptr(y), _ptr(s), _ptr(coef), _ptr(inp), _ptr(xpos), _ptr(ypos),
-            _ptr(gin), _ptr(gx), _ptr(gy), _ptr(ws), nbytes, B, C, H, W, 1, _stream(inp))
+            _ptr(gin), _ptr(gx), _ptr(gy), _ptr(ws), nbytes, B, C, H, W, 1, int(dyp),
+            _stream(inp))
     _lib.check(rc, "sgcn_tshift_bwd_bnin")
     return gin, (pp if pp is not None else gx), gy
 
@@ -757,18 +773,22 @@ def bn_apply(x, st: BnStats, per_joint, r=None, rst: BnStats = None, relu=False,
 
 def bn_bwd_reduce(dy, y, relu, x, st: BnStats, per_joint, r=None, rst: BnStats = None,
                   dy_coef=None):
+    """``dy`` (B, C): one value per plane of x. ``relu=False, y=None``: a dy that already
+    carries the ReLU mask."""
     check_input(dy, "grad_output")
     B, C, T, V = x.shape
+    dyp = _plane_dy(dy, x)
     dev = x.device
     part = torch.empty((B * C * (V if per_joint else 1) * 2,), device=dev, dtype=_F32)
     rpart = torch.empty((B * C * 2,), device=dev, dtype=_F32) if r is not None else None
-    nb = 4 * x.numel() * (2 + (y is not None) + (r is not None))
+    nb = 4 * (dy.numel() + x.numel() * (1 + (y is not None) + (r is not None)))
     with _timed("bn_bwd_reduce", 0, nb, x, _shp(x)):
         rc = _lib.load().sgcn_bn_bwd_reduce(_ptr(dy), _ptr(y), int(relu), _ptr(x),
                                             _ptr(st.mean), _ptr(st.invstd), int(per_joint),
                                             _ptr(r), _ptr(rst.mean) if rst else None,
                                             _ptr(rst.invstd) if rst else None, _ptr(dy_coef),
-                                            _ptr(part), _ptr(rpart), B, C, T, V, _stream(x))
+                                            _ptr(part), _ptr(rpart), B, C, T, V, int(dyp),
+                                            _stream(x))
     _lib.check(rc, "sgcn_bn_bwd_reduce")
     return part, rpart
 
@@ -898,21 +918,25 @@ def gcn_gather(x0, m):
     return xg
 
 
-def gcn_dx_finish(dxt, x0, m, add1=None, add2=None, prev=None, add2_mask=None):
+def gcn_dx_finish(dxt, x0, m, add1=None, add2=None, prev=None, add2_mask=None,
+                  mask_dx=False):
     """Returns (dx, dmask partials[, prev_part]); ``prev`` = (S, BnStats) of the previous
-    unit's bn2 adds its backward-reduce partials (see sgcn_gcn_dx_finish)."""
+    unit's bn2 adds its backward-reduce partials (see sgcn_gcn_dx_finish). ``mask_dx``: dx
+    is stored as dx * (x0 > 0). ``add2`` (B, C) with ``add2_mask``: one value per plane."""
     B, C, T, V = dxt.shape
+    flags = int(bool(mask_dx)) | (2 if add2 is not None and _plane_dy(add2, dxt) else 0)
     dx = torch.empty_like(dxt)
     part = torch.empty((B * C * V,), device=dxt.device, dtype=_F32)
     pp = torch.empty((B * C * 2,), device=dxt.device, dtype=_F32) if prev is not None else None
     ps, pst = prev if prev is not None else (None, None)
-    nb = 4 * dxt.numel() * (3 + sum(t is not None for t in (add1, add2, add2_mask, ps)))
+    nb = 4 * (dxt.numel() * (3 + sum(t is not None for t in (add1, add2_mask, ps))) +
+              (add2.numel() if add2 is not None else 0))
     with _timed("gcn_dx_finish", 0, nb, dxt, _shp(dxt)):
         rc = _lib.load().sgcn_gcn_dx_finish(_ptr(dxt), _ptr(x0), _ptr(m), _ptr(add1),
                                             _ptr(add2), _ptr(add2_mask), _ptr(dx), _ptr(part),
                                             _ptr(ps), _ptr(pst.mean) if pst else None,
                                             _ptr(pst.invstd) if pst else None, _ptr(pp), B, C,
-                                            T, V, _stream(dxt))
+                                            T, V, flags, _stream(dxt))
     _lib.check(rc, "sgcn_gcn_dx_finish")
     return (dx, part) if prev is None else (dx, part, pp)
 
@@ -984,11 +1008,23 @@ def pool(x, N, M):
     return out
 
 
-def pool_bwd(dout, shape, N, M):
+def pool_bwd(dout, shape, N, M, planes=False):
+    """The pooling's backward: the (N*M, C, T, V) gradient, or with ``planes`` only its
+    (N*M, C) plane values — the one value each (T, V) plane holds, same expression and
+    rounding (sgcn_pool_bwd_planes) — for consumers that take a per-plane gradient."""
     check_input(dout, "grad_output")
-    dx = torch.empty(shape, device=dout.device, dtype=_F32)
     C = shape[1]
-    P = dx.numel() // max(1, N * M * C)
+    P = 1
+    for d in shape[2:]:
+        P *= d
+    if planes:
+        dp = torch.empty((N * M, C), device=dout.device, dtype=_F32)
+        with _timed("pool", 0, 4 * (dout.numel() + dp.numel()), dout):
+            rc = _lib.load().sgcn_pool_bwd_planes(_ptr(dout), _ptr(dp), N, M, C, P,
+                                                  _stream(dout))
+        _lib.check(rc, "sgcn_pool_bwd_planes")
+        return dp
+    dx = torch.empty(shape, device=dout.device, dtype=_F32)
     with _timed("pool", 0, 4 * dx.numel(), dout):
         rc = _lib.load().sgcn_pool_bwd(_ptr(dout), _ptr(dx), N, M, C, P, _stream(dout))
     _lib.check(rc, "sgcn_pool_bwd")

@@ -233,5 +233,6 @@ def linked_units(units):
             u.__dict__.pop("_next_unit", None)
             u.__dict__.pop("_off_path", None)
             u.__dict__.pop("_prev_tail", None)
+            u.__dict__.pop("_prev_out", None)
             u.gcn1.__dict__.pop("_gather_cache", None)
             u.gcn1.__dict__.pop("_mask_ready", None)

@@ -55,7 +55,7 @@ OP_CLASSES = {
                   "tshift_pos_finalize_kernel"), ()),
     "head": (("head_moments_kernel", "head_apply_kernel", "head_bwd_reduce_kernel",
               "head_bwd_apply_kernel", "modalities_kernel"), ()),
-    "pool": (("pool_kernel", "pool_bwd_kernel"), ()),
+    "pool": (("pool_kernel", "pool_bwd_kernel", "pool_bwd_planes_kernel"), ()),
 }
 # FETCH_SIZE correction per kernel: x2 for reads whose wave instructions cover whole 128-B
 # lines (calibrated with known-byte kernels: profiles/r02_calib, profiles/r03_fetchcal); the
