@@ -23,12 +23,17 @@ Shift_tcn (shift_gcn.py:65-74)
            gcn BN-backward kernels evaluate it on the fly)
 TCN_GCN_unit (shift_gcn.py:160-162): bn2 apply + residual (0 / identity / tcn conv+BN) +
   ReLU is ONE bn_apply launch; its backward ONE reduce + ONE apply.
+Neighbouring units of a chain (shift_gcn.linked_units) share launches: a unit's tail writes
+  the next unit's gathered gcn input; the next unit's gcn_dx_finish makes this unit's bn2
+  backward partials and stores its output gradient pre-masked. It all travels in one _Link per
+  edge and linked_units block (from _Pos forward, UnitSaved backward), nothing on a module.
 
 Everything runs on torch's current stream; intermediate buffers come from torch's
 caching allocator, so a whole training step can be captured in a hipGraph.
 """
 from __future__ import annotations
 
+import collections
 import os
 import threading
 
@@ -248,9 +253,11 @@ class GcnSaved:
     __slots__ = ("x0", "xg", "Z", "zst", "D0", "dst", "H", "m", "h_moments")
 
 
-def gcn_forward(mod, x0, training, off=False):
+def gcn_forward(mod, x0, training, off=False, gathered=None, prepared=None):
     """``off``: the down conv branch (contraction + statistics) runs on the side stream,
-    concurrently with the gcn contraction, joined before the apply that reads it."""
+    concurrently with the gcn contraction, joined before the apply that reads it.
+    ``gathered`` = (shift_in gather of x0 * mask, mask) made by the previous unit's tail launch
+    (unit_forward); else gathered here, with the mask ``prepared`` for this call (_mask_of)."""
     B, Cin, T, V = x0.shape
     Cout = mod.out_channels
     D0 = dst = None
@@ -264,11 +271,10 @@ def gcn_forward(mod, x0, training, off=False):
                 dst = ops.bn_finalize(ops.moments(D0, False), B, Cout, T * V, bn)
             else:
                 dst = ops.bn_eval_coef(bn, Cout)
-    cache = mod.__dict__.pop("_gather_cache", None)
-    if cache is not None and cache[0] is x0:
-        xg, m = cache[1], cache[2]    # made by the previous unit's tail from its registers
+    if gathered is not None:
+        xg, m = gathered              # made by the previous unit's tail from its registers
     else:
-        m = _mask_of(mod)
+        m = _mask_of(mod, prepared)
         xg = ops.gcn_gather(x0, m)    # shift_in gather * mask, once (reused by the dW)
     Z = _empty(B, Cout, T, V, like=x0)
     # Z is stored BEFORE shift_out (plain contraction stores) and the BatchNorm kernels
@@ -289,13 +295,14 @@ def gcn_forward(mod, x0, training, off=False):
     return H, s
 
 
-def _mask_of(gcn):
-    """tanh(Feature_Mask) + 1 of a Shift_gcn: the one linked_units prepared for this call
-    (all units' in one launch), else its own launch (once per version of the mask)."""
+def _mask_of(gcn, prepared=None):
+    """tanh(Feature_Mask) + 1 of a Shift_gcn: the one ``prepared`` for this call
+    (prepare_masks: all units' in one launch; it reaches TCN_GCN_units only, a Shift_gcn
+    called on its own makes its own) if the mask is still the tensor and version it was made
+    from, else its own launch (in eval mode once per version of the mask)."""
     fm = gcn.Feature_Mask
-    r = gcn.__dict__.get("_mask_ready")
-    if r is not None and r[0] is fm and r[1] == fm._version:
-        return r[2]
+    if prepared is not None and prepared[0] is fm and prepared[1] == fm._version:
+        return prepared[2]
     if gcn.training:
         return ops.mask_prep(fm)
     return ops.cached(gcn, "_sgcn_mask", ops._src_key((fm,)), lambda: ops.mask_prep(fm),
@@ -304,26 +311,28 @@ def _mask_of(gcn):
 
 def prepare_masks(gcns):
     """Every Shift_gcn's mask for one forward in one launch (sgcn_mask_prep_many); in eval
-    mode once per version of the masks (ops.cached)."""
+    mode once per version of the masks (ops.cached). Returns one (Feature_Mask, its version,
+    mask) per Shift_gcn: what _mask_of takes as ``prepared``."""
     fms = [g.Feature_Mask for g in gcns]
     if any(g.training for g in gcns):
         ms = ops.mask_prep_many(fms)
     else:
         ms = ops.cached(gcns[0], "_sgcn_masks", ops._src_key(fms) + tuple(map(id, gcns)),
                         lambda: ops.mask_prep_many(fms), fms[0].device)
-    for g, m in zip(gcns, ms):
-        g.__dict__["_mask_ready"] = (g.Feature_Mask, g.Feature_Mask._version, m)
+    return [(fm, fm._version, m) for fm, m in zip(fms, ms)]
 
 
-def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, extra_out=None,
-                 pre6=None, off=False, mask_dx=False):
-    """Returns (dx0, {param_name: grad}). With ``dy_coef`` ([3, Cout]) the incoming
-    gradient is dH = k1*dH_arg + k2*H + k3 (Shift_tcn.bn's input gradient), evaluated
-    on the fly by the BN-backward kernels instead of being materialised. ``pre6`` =
-    (six-sum partials, Shift_tcn.bn stats) from sgcn_tshift_bwd_gbn: bn's backward
+def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, pre6=None,
+                 off=False, mask_dx=False):
+    """Returns (dx0, {param_name: grad}, prev_part). With ``dy_coef`` ([3, Cout]) the
+    incoming gradient is dH = k1*dH_arg + k2*H + k3 (Shift_tcn.bn's input gradient),
+    evaluated on the fly by the BN-backward kernels instead of being materialised. ``pre6``
+    = (six-sum partials, Shift_tcn.bn stats) from sgcn_tshift_bwd_gbn: bn's backward
     partials were made by the shift_in backward launch (no reduce pass here). ``off``:
     the weight-gradient launches go to the side stream (see _OffPath). ``mask_dx``: dx0 is
-    returned as dx0 * (x0 > 0) (only without a down conv, whose dx is accumulated after)."""
+    returned as dx0 * (x0 > 0) (only without a down conv, whose dx is accumulated after).
+    ``extra_dx`` = (tensor, its ReLU-mask operand or None), added into dx0. ``prev`` = (S, bn2
+    stats) of the previous unit (x0 = its out): also makes its bn2 partials, ``prev_part``."""
     x0 = s.x0
     assert not (mask_dx and mod.has_down)
     B, Cin, T, V = x0.shape
@@ -370,14 +379,10 @@ def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, e
     with _OffPath(off, dZ, s.xg):
         ops.pw_dw(PV(dZ), PV(s.xg), dLW, Cout, Cin, T, V, transpose=True, dbias=dLb)
     g["Linear_weight"], g["Linear_bias"] = _late(dLW, off), _late(dLb, off)
-    a2, a2m = extra_dx if isinstance(extra_dx, tuple) else (extra_dx, None)
-    if prev is not None:   # also the previous unit's bn2 backward partials (x0 = its out)
-        dx, mpart, extra_out["prev_part"] = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id,
-                                                              add2=a2, prev=prev,
-                                                              add2_mask=a2m, mask_dx=mask_dx)
-    else:
-        dx, mpart = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id, add2=a2, add2_mask=a2m,
-                                      mask_dx=mask_dx)
+    a2, a2m = extra_dx or (None, None)
+    res = ops.gcn_dx_finish(dXt, x0, s.m, add1=g_id, add2=a2, prev=prev, add2_mask=a2m,
+                            mask_dx=mask_dx)
+    dx, mpart, prev_part = res if prev is not None else (*res, None)
     dmask = ops.grad_like(mod.Feature_Mask)
     fm = mod.Feature_Mask
     if BATCH_SIDE and (off or _defer_ok((fm,))):
@@ -395,7 +400,7 @@ def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, e
         with _OffPath(off, dD0, x0):
             ops.pw_dw(PV(dD0), PV(x0), dWd, Cout, Cin, T, V, dbias=dbd)
         g["down.0.weight"], g["down.0.bias"] = _late(dWd, off), _late(dbd, off)
-    return dx, g
+    return dx, g, prev_part
 
 
 # ======================================================================================
@@ -445,16 +450,16 @@ def convbn_infer_folded(mod, x):
     return R
 
 
-def gcn_infer_z(mod, x0):
+def gcn_infer_z(mod, x0, gathered=None, prepared=None):
     """Inference Shift_gcn up to its contraction output: (Z, zst, res, res_stats); the
-    BN1d + down/identity + ReLU are applied by the consumer (sgcn_tshift_fwd_pre)."""
+    BN1d + down/identity + ReLU are applied by the consumer (sgcn_tshift_fwd_pre).
+    ``gathered``, ``prepared``: as in gcn_forward."""
     B, Cin, T, V = x0.shape
     Cout = mod.out_channels
-    cache = mod.__dict__.pop("_gather_cache", None)
-    if cache is not None and cache[0] is x0:
-        xg = cache[1]
+    if gathered is not None:
+        xg = gathered[0]
     else:
-        xg = ops.gcn_gather(x0, _mask_of(mod))
+        xg = ops.gcn_gather(x0, _mask_of(mod, prepared))
     Z = _empty(B, Cout, T, V, like=x0)
     ops.pw_fwd(mod.Linear_weight, True, mod.Linear_bias, PV(xg), PV(Z, 1, +1), Cout, Cin, T, V)
     zst = ops.bn_eval_coef(mod.bn, Cout * V, perm_V=V)
@@ -519,17 +524,18 @@ def tcn_core_forward(mod, H, training, h_moments=None, tail=None, pre=None):
 
 
 def tcn_core_backward(mod, s: TcnSaved, dS, materialize_dx=True, gpre=None, gcn_z=None,
-                      out=None, off=False):
-    """dS: gradient w.r.t. S (pre-bn2). Returns (dH, grads), or ((dA, coef), grads) with
-    ``materialize_dx=False`` (dH = coef[0]*dA + coef[1]*H + coef[2], fused downstream).
-    ``gcn_z`` = (Z, zst[, (D0, dst)]) of the producing Shift_gcn: its BatchNorm's (and its
-    down BatchNorm's) backward sums come out of the shift_in backward launch, returned as
-    out["pre6"] = (z sums, Shift_tcn.bn stats, down sums or None)."""
+                      off=False):
+    """dS: gradient w.r.t. S (pre-bn2). Returns (dH, grads, pre6), or ((dA, coef), grads,
+    pre6) with ``materialize_dx=False`` (dH = coef[0]*dA + coef[1]*H + coef[2], fused
+    downstream). ``gcn_z`` = (Z, zst[, (D0, dst)]) of the producing Shift_gcn: its
+    BatchNorm's (and its down BatchNorm's) backward sums come out of the shift_in backward
+    launch, returned as pre6 = (z sums, Shift_tcn.bn stats, down sums or None); else pre6
+    is None."""
     H = s.H
     B, C, T, V = H.shape
     Cout = mod.out_channels
     si, so = mod.shift_in, mod.shift_out
-    g = {}
+    g, pre6 = {}, None
     # (off: each shift backward leaves its position-gradient partials for a finalize on the
     # side stream, _pos_grads: the positions' gradients only feed the optimizer)
     if gpre is not None:   # dS = bn2's input gradient, formed inside the shift backward
@@ -558,7 +564,7 @@ def tcn_core_backward(mod, s: TcnSaved, dS, materialize_dx=True, gpre=None, gcn_
                                  gcn_z[1], defer_pos=off, down=down,
                                  pos_out=_pos_alloc(si, off))
         dA, gx, gy, part, zpart = res[:5]
-        out["pre6"] = (zpart, s.ast, res[5] if down is not None else None)
+        pre6 = (zpart, s.ast, res[5] if down is not None else None)
     else:
         dA, gx, gy, part = ops.tshift_bwd(
             dAs, H, si.xpos.detach(), si.ypos.detach(), si.stride, scale=s.ast.scale,
@@ -567,9 +573,9 @@ def tcn_core_backward(mod, s: TcnSaved, dS, materialize_dx=True, gpre=None, gcn_
     coef, g["bn.weight"], g["bn.bias"] = ops.bn_bwd_finalize(part, B, C, B * T * V, s.ast,
                                                              mod.bn)
     if not materialize_dx:
-        return (dA, coef), g       # dH = k1*dA + k2*H + k3, left for the consumer to fuse
+        return (dA, coef), g, pre6   # dH = k1*dA + k2*H + k3, left for the consumer to fuse
     dH = ops.bn_bwd_apply(dA, None, False, H, coef, False)
-    return dH, g
+    return dH, g, pre6
 
 
 # ======================================================================================
@@ -613,19 +619,69 @@ def convbn_dx_and_dw(mod, s: ConvBnSaved, dRc, dx, accumulate, off=False):
 # ======================================================================================
 # TCN_GCN_unit
 # ======================================================================================
+class _Link:
+    """One edge (producer unit -> consumer unit) of ONE linked_units block. Forward, set by the
+    producer: ``out`` (its output, the identity token), ``xg``/``gm`` (the consumer's gathered
+    gcn input and mask, from the producer's tail launch), ``tail`` = the producer's (S, bn2
+    stats) if the consumer's gcn_dx_finish may make its bn2 backward partials, ``full`` = the
+    consumer forms out's COMPLETE gradient. Backward, set by the consumer: ``dx`` (its input
+    gradient, the identity token), ``prev_part`` (those partials), ``masked`` (dx stored with
+    out's ReLU mask applied). Readers check the token (``out is x``, ``dx is dout``): another
+    tensor, or a gradient autograd summed with another, takes the unfused forms. The consumer
+    takes the forward fields into its own saved state, so a producer called again within the
+    block cannot change what an earlier consumer call's backward uses."""
+
+    __slots__ = ("out", "xg", "gm", "tail", "full", "dx", "prev_part", "masked")
+
+    def __init__(self):
+        self.out = self.xg = self.gm = self.tail = self.dx = self.prev_part = None
+        self.full = self.masked = False
+
+    def take(self, x):
+        """((xg, gm), tail, full) if ``x`` IS the output they were made from, else (None,
+        None, False); the forward fields are dropped either way (one consumer call each)."""
+        r = ((self.xg, self.gm), self.tail, self.full) if self.out is x else (None, None, False)
+        self.out = self.xg = self.gm = self.tail = None
+        self.full = False
+        return r
+
+
+# A unit's place in one linked_units block (its ``_link_pos`` attribute meanwhile): its links,
+# the next unit, whether it may use the side stream, its own and the next unit's mask as
+# prepared for this block
+_Pos = collections.namedtuple("_Pos", "link_in link_out nxt off mask nxt_mask",
+                              defaults=(None, None, None, False, None, None))
+
+
+def chain_positions(units):
+    """One _Pos per unit of a chain (see linked_units), with fresh links between neighbours
+    and every unit's tanh(Feature_Mask) + 1 made in one launch (prepare_masks). TAIL_MAIN
+    bit 2: the chain's first unit keeps its weight gradients on the main stream."""
+    masks = prepare_masks([u.gcn1 for u in units])
+    links = [None] + [_Link() for _ in units[1:]] + [None]
+    nxt, masks = list(units[1:]) + [None], masks + [None]
+    return [_Pos(links[i], links[i + 1], nxt[i], bool(i or not TAIL_MAIN & 2), masks[i],
+                 masks[i + 1]) for i in range(len(units))]
+
+
 class UnitSaved:
-    __slots__ = ("x", "gs", "ts", "rs", "out", "prev", "off", "pm")
+    __slots__ = ("x", "gs", "ts", "rs", "out", "link_in", "link_out", "prev", "full", "off")
 
 
 def unit_forward(unit, x, training):
-    consumer = unit.__dict__.get("_gather_consumer")
+    pos = unit.__dict__.get("_link_pos") or _Pos()
+    li, lo, nxt = pos.link_in, pos.link_out, pos.nxt
+    # the previous unit's tail launch wrote this unit's gathered input (if x is its out);
+    # prev, full: that unit's (S, bn2 stats) and whether this one may mask for it (_Link)
+    gathered, prev, full = li.take(x) if li is not None else (None, None, False)
+    li = li if gathered is not None else None
     if (not training and _INFER.active and
             x.shape[2] * x.shape[3] <= ops.TAIL_MAX_PLANE):
         # inference (no backward can follow): the Shift_gcn tail is fused into shift_in,
         # the unit tail into shift_out; neither H nor S is written
         # the Shift_gcn tail (BN1d eval + down/identity + ReLU) is formed in the shift_in
         # launch's staging
-        pre = gcn_infer_z(unit.gcn1, x)
+        pre = gcn_infer_z(unit.gcn1, x, gathered, pos.mask)
         r = rst = None
         if unit.residual_kind == "conv":
             if EVAL_FOLD:
@@ -634,38 +690,19 @@ def unit_forward(unit, x, training):
                 r, rst, _ = convbn_core_forward(unit.residual, x, training)
         elif unit.residual_kind == "identity":
             r = x
-        gm = _mask_of(consumer) if consumer is not None else None
+        gm = _mask_of(nxt.gcn1, pos.nxt_mask) if lo is not None else None
         out, xg_next = tcn_core_forward(unit.tcn1, None, training, tail=(r, rst, gm),
                                         pre=pre)
-        if gm is not None:
-            consumer.__dict__["_gather_cache"] = (out, xg_next, gm)
+        if lo is not None:
+            lo.out, lo.xg, lo.gm, lo.tail, lo.full = out, xg_next, gm, None, False
         return out, None
-    # the previous unit's tail (its out is x): its bn2 backward partials are made by this
-    # unit's gcn_dx_finish, which reads x anyway (see unit_backward); prev = (bn2 input
-    # operand for ops.gcn_dx_finish, that unit)
-    prev = unit.__dict__.pop("_prev_tail", None)
-    prev = prev[1:] if prev is not None and prev[0] is x else None
-    # the previous linked unit, when x is its output and this unit's gcn_dx_finish forms x's
-    # COMPLETE gradient (no residual conv, no gcn down conv: their dx is added after): that
-    # launch may store the gradient with x's ReLU mask applied (see _unit_backward)
-    pm = unit.__dict__.pop("_prev_out", None)
-    pm = pm[1] if (pm is not None and pm[0] is x and unit.residual_kind != "conv" and
-                   not unit.gcn1.has_down) else None
     # linked chains only; not while a hipGraph is being captured (the graph replays one
     # stream's launches in order)
-    off = (ASYNC_DW and bool(unit.__dict__.get("_off_path")) and
-           not torch.cuda.is_current_stream_capturing())
-    # the next unit's gcn mask (tanh(Feature_Mask) + 1), needed by this unit's tail launch:
-    # a tiny kernel, made on the side stream off the critical path
-    mp = None
-    if consumer is not None:
-        if "_mask_ready" in consumer.__dict__:   # prepared with the chain's others
-            gm = _mask_of(consumer)
-        else:
-            mp = _OffPath(off, consumer.Feature_Mask)
-            with mp:
-                gm = ops.mask_prep(consumer.Feature_Mask)
-    H, gs = gcn_forward(unit.gcn1, x, training, off=off)
+    off = ASYNC_DW and pos.off and not torch.cuda.is_current_stream_capturing()
+    # the next unit's gcn mask (tanh(Feature_Mask) + 1), needed by this unit's tail launch
+    gm = _mask_of(nxt.gcn1, pos.nxt_mask) if lo is not None else None
+    H, gs = gcn_forward(unit.gcn1, x, training, off=off, gathered=gathered,
+                        prepared=pos.mask)
     rs = None
     if unit.residual_kind == "conv":
         # the residual conv branch runs on the side stream, concurrently with Shift_tcn
@@ -673,12 +710,7 @@ def unit_forward(unit, x, training):
         with res:
             Rc, rst, rs = convbn_core_forward(unit.residual, x, training)
     S, sst, ts = tcn_core_forward(unit.tcn1, H, training, h_moments=gs.h_moments)
-    # the next unit's Shift_gcn (set by Model.forward_planes for the duration of a call):
-    # its gathered, masked input is written by this tail launch too
-    if mp is not None:
-        mp.wait()
-    elif consumer is None:
-        gm = None
+    # (gm: the next unit's gathered, masked gcn input is written by this tail launch too)
     if unit.residual_kind == "conv":
         res.wait()
         out = ops.bn_apply(S, sst, False, r=Rc, rst=rst, relu=True, gather_m=gm)
@@ -686,21 +718,18 @@ def unit_forward(unit, x, training):
         out = ops.bn_apply(S, sst, False, r=x, relu=True, gather_m=gm)
     else:
         out = ops.bn_apply(S, sst, False, relu=True, gather_m=gm)
-    if gm is not None:
-        out, xg_next = out
-        consumer.__dict__["_gather_cache"] = (out, xg_next, gm)
-    nxt = unit.__dict__.get("_next_unit")
-    # the next unit's gcn_dx_finish may produce this unit's bn2 backward partials only if
-    # the dx it reads is this unit's COMPLETE output gradient: no residual conv (whose dx is
-    # added after) and no gcn down conv (whose dx is accumulated after gcn_dx_finish)
-    if (nxt is not None and unit.residual_kind != "conv" and nxt.residual_kind != "conv"
-            and not nxt.gcn1.has_down):
-        nxt.__dict__["_prev_tail"] = (out, (S, sst), unit)
-    if nxt is not None:
-        nxt.__dict__["_prev_out"] = (out, unit)
+    if lo is not None:
+        out, lo.xg = out
+        lo.out, lo.gm = out, gm
+        # the next unit's gcn_dx_finish reads ``out`` anyway. Where it forms out's COMPLETE
+        # gradient (no residual conv, no gcn down conv there: their dx is added after) it may
+        # store it pre-masked and, if this unit has no residual conv either (its reduce would
+        # need that branch's operands), make this unit's bn2 partials (see _unit_backward)
+        lo.full = nxt.residual_kind != "conv" and not nxt.gcn1.has_down
+        lo.tail = (S, sst) if lo.full and unit.residual_kind != "conv" else None
     s = UnitSaved()
-    s.x, s.gs, s.ts, s.rs, s.out, s.prev = x, gs, ts, rs, out, prev
-    s.off, s.pm = off, pm
+    s.x, s.gs, s.ts, s.rs, s.out, s.off = x, gs, ts, rs, out, off
+    s.link_in, s.link_out, s.prev, s.full = li, lo, prev, full
     return out, s
 
 
@@ -752,79 +781,74 @@ def _premask_ok(unit, x, off):
         return False
 
 
+def _fused_tail(unit, To, V):
+    """Whether the unit's backward forms bn2's input gradient inside the shift_out backward
+    (sgcn_tshift_bwd_bnin) instead of writing it; only this form takes a per-plane dout."""
+    return (unit.residual_kind != "conv" and unit.tcn1.shift_out.stride == 1 and
+            ops.ra_fits(To * V, V))
+
+
+def premasked(s: UnitSaved, dout):
+    """Whether ``dout`` arrived marked for this call: it IS the tensor the next unit's
+    gcn_dx_finish stored with this unit's ReLU mask applied."""
+    lo = s.link_out
+    return lo is not None and lo.masked and lo.dx is dout
+
+
 def _unit_backward(unit, s: UnitSaved, dout, off):
     """``dout``: the unit's output gradient, (B, C, To, V), or (B, C) = one value per plane
-    (_BlockFunction.backward; first branch below only)."""
+    (_BlockFunction.backward; with the fused tail only)."""
     ts = s.ts
     S = ts.S
-    so = unit.tcn1.shift_out
     B, Cout, To, V = S.shape
     kind = unit.residual_kind
+    li, lo = s.link_in, s.link_out
     g = {}
     # the next unit's gcn_dx_finish stored dout with this unit's ReLU mask applied
     # (dout * (out > 0): exactly what every consumer below forms from (dout, out)), so no
     # kernel of this backward reads ``out``. Told by identity: a gradient autograd summed
     # with another contribution is a different tensor and takes the unmasked forms (also
     # correct on a masked tensor: masking is idempotent)
-    pmk = unit.__dict__.pop("_premasked", None)
-    masked = pmk is not None and pmk is dout
-    y, relu = (None, False) if masked else (s.out, True)
+    y, relu = (None, False) if premasked(s, dout) else (s.out, True)
     # this unit masks for the previous one
-    mask_dx = s.pm is not None and _premask_ok(unit, s.x, off)
-    cached = unit.__dict__.pop("_bwd_part", None)
-    if cached is not None and cached[0] is dout and kind != "conv":
-        part, rpart = cached[1], None   # made by the next unit's gcn_dx_finish
-    elif kind == "conv":
-        part, rpart = ops.bn_bwd_reduce(dout, y, relu, S, ts.sst, False, r=s.rs.Rc,
-                                        rst=s.rs.rst)
-    else:
-        part, rpart = ops.bn_bwd_reduce(dout, y, relu, S, ts.sst, False)
+    mask_dx = s.full and _premask_ok(unit, s.x, off)
+    part = rpart = None
+    if lo is not None:   # the link's backward fields are consumed here, whatever dout is
+        if lo.dx is dout:
+            part = lo.prev_part   # made by the next unit's gcn_dx_finish (kind != "conv")
+        lo.dx, lo.prev_part, lo.masked = None, None, False
+    if part is None:
+        r, rst = (s.rs.Rc, s.rs.rst) if kind == "conv" else (None, None)
+        part, rpart = ops.bn_bwd_reduce(dout, y, relu, S, ts.sst, False, r=r, rst=rst)
     coef2, g["tcn1.bn2.weight"], g["tcn1.bn2.bias"] = ops.bn_bwd_finalize(
         part, B, Cout, B * To * V, ts.sst, unit.tcn1.bn2)
-    if kind != "conv" and so.stride == 1 and ops.ra_fits(To * V, V):
+    dS = gpre = dres = extra = None
+    if _fused_tail(unit, To, V):
         # neither dS nor the identity-residual gradient is written: the shift_out backward
         # forms dS while staging, gcn_dx_finish forms dout*(out > 0)
-        fo = {}
-        (dA, coefA), gt = tcn_core_backward(unit.tcn1, ts, None, materialize_dx=False,
-                                            gpre=(dout, y, coef2), gcn_z=_gcn_z(unit, s),
-                                            out=fo, off=off)
-        g.update({"tcn1." + k: v for k, v in gt.items()})
-        extra = {}
-        dx, gg = gcn_backward(unit.gcn1, s.gs, dA,
-                              extra_dx=(dout, y) if kind == "identity" else None,
-                              dy_coef=coefA, prev=None if s.prev is None else s.prev[0],
-                              extra_out=extra, pre6=fo.get("pre6"), off=off, mask_dx=mask_dx)
-        if s.prev is not None:
-            s.prev[1].__dict__["_bwd_part"] = (dx, extra["prev_part"])
-        if mask_dx:
-            s.pm.__dict__["_premasked"] = dx
-        g.update({"gcn1." + k: v for k, v in gg.items()})
-        return dx, g
-    dS = torch.empty_like(S)
-    dres = None
-    if kind == "conv":
-        coefR, g["residual.bn.weight"], g["residual.bn.bias"] = ops.bn_bwd_finalize(
-            rpart, B, Cout, B * To * V, s.rs.rst, unit.residual.bn)
-        dres = torch.empty_like(s.rs.Rc)
-        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, r=s.rs.Rc, rcoef=coefR, dr=dres,
-                         dx=dS)
-    elif kind == "identity":
-        dres = torch.empty_like(s.x)
-        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, dr=dres, dx=dS)
+        gpre = (dout, y, coef2)
+        if kind == "identity":
+            extra = (dout, y)
     else:
-        ops.bn_bwd_apply(dout, y, relu, S, coef2, False, dx=dS)
-    fo = {}
-    (dA, coefA), gt = tcn_core_backward(unit.tcn1, ts, dS, materialize_dx=False,
-                                        gcn_z=_gcn_z(unit, s), out=fo, off=off)
+        dS = torch.empty_like(S)
+        if kind == "conv":
+            coefR, g["residual.bn.weight"], g["residual.bn.bias"] = ops.bn_bwd_finalize(
+                rpart, B, Cout, B * To * V, s.rs.rst, unit.residual.bn)
+            dres = torch.empty_like(s.rs.Rc)
+            ops.bn_bwd_apply(dout, y, relu, S, coef2, False, r=s.rs.Rc, rcoef=coefR, dr=dres,
+                             dx=dS)
+        else:
+            if kind == "identity":
+                dres = torch.empty_like(s.x)
+                extra = (dres, None)
+            ops.bn_bwd_apply(dout, y, relu, S, coef2, False, dr=dres, dx=dS)
+    (dA, coefA), gt, pre6 = tcn_core_backward(unit.tcn1, ts, dS, materialize_dx=False,
+                                              gpre=gpre, gcn_z=_gcn_z(unit, s), off=off)
+    dx, gg, prev_part = gcn_backward(unit.gcn1, s.gs, dA, extra_dx=extra, dy_coef=coefA,
+                                     prev=s.prev, pre6=pre6, off=off, mask_dx=mask_dx)
+    if s.prev is not None or mask_dx:   # (only with a matched link_in; dx is final here)
+        li.dx, li.prev_part, li.masked = dx, prev_part, mask_dx
     g.update({"tcn1." + k: v for k, v in gt.items()})
-    extra = {}
-    dx, gg = gcn_backward(unit.gcn1, s.gs, dA, extra_dx=dres if kind == "identity" else None,
-                          dy_coef=coefA, prev=None if s.prev is None else s.prev[0],
-                          extra_out=extra, pre6=fo.get("pre6"), off=off, mask_dx=mask_dx)
-    if s.prev is not None:   # kind != "conv" and no gcn down conv: dx is final here
-        s.prev[1].__dict__["_bwd_part"] = (dx, extra["prev_part"])
-    if mask_dx:
-        s.pm.__dict__["_premasked"] = dx
     g.update({"gcn1." + k: v for k, v in gg.items()})
     if kind == "conv":
         gr = convbn_dx_and_dw(unit.residual, s.rs, dres, dx, accumulate=True, off=off)
@@ -865,7 +889,7 @@ ASYNC_DW = int(os.environ.get("SGCN_ASYNC_DW", "1"))
 # A linked unit's output gradient arrives with its ReLU mask already applied (stored by the
 # next unit's gcn_dx_finish, which reads that output anyway), and the pool's gradient as one
 # value per plane, so no backward kernel reads a unit's output only for `out > 0` and the
-# pool's expanded gradient is never written (_unit_backward, _plane_dy). Bit-identical.
+# pool's expanded gradient is never written (_unit_backward, _unit_dy_planes). Bit-identical.
 # A/B knob: 0 = every consumer re-reads the output for its mask, as before.
 PREMASK = int(os.environ.get("SGCN_PREMASK", "1"))
 
@@ -907,7 +931,7 @@ class _BlockFunction(torch.autograd.Function):
                 "called a second time; its saved activations are released after the first "
                 "backward (retain_graph=True / double backward is not supported)")
         _, bwd = ctx.impl
-        dyp = _plane_dy(ctx, dy)
+        dyp = _unit_dy_planes(ctx, dy)
         dx, grads = bwd(ctx.module, ctx.saved, dy.contiguous() if dyp is None else dyp)
         ctx.saved = None
         out = []
@@ -920,18 +944,13 @@ class _BlockFunction(torch.autograd.Function):
         return (None, None, dx) + tuple(out)
 
 
-def _plane_dy(ctx, dy):
+def _unit_dy_planes(ctx, dy):
     """The (B, C) plane values of an output gradient expanded over (T, V) (both strides 0:
     the pool's backward, ``unit(x).mean().backward()``), when the unit's backward takes them
-    in place of the materialised tensor (the fused branch of _unit_backward: no residual
-    conv, stride 1, ra_fits); else None."""
+    in place of the materialised tensor (_fused_tail); else None."""
     if not (PREMASK and ctx.impl is UNIT_IMPL and dy.dim() == 4 and dy.stride(2) == 0 and
-            dy.stride(3) == 0 and isinstance(ctx.saved, UnitSaved)):
-        return None
-    unit = ctx.module
-    To, V = dy.shape[2], dy.shape[3]
-    if (unit.residual_kind == "conv" or unit.tcn1.shift_out.stride != 1 or
-            not ops.ra_fits(To * V, V)):
+            dy.stride(3) == 0 and isinstance(ctx.saved, UnitSaved) and
+            _fused_tail(ctx.module, dy.shape[2], dy.shape[3])):
         return None
     return dy[:, :, 0, 0].contiguous()
 
@@ -957,10 +976,6 @@ def run_block(impl, module, x):
         _INFER.active = prev
 
 
-def _gcn_standalone_bwd(mod, s, dy):
-    return gcn_backward(mod, s, dy)
-
-
 def _tcn_standalone_fwd(mod, H, training):
     S, sst, ts = tcn_core_forward(mod, H, training)
     y = ops.bn_apply(S, sst, False)
@@ -973,7 +988,7 @@ def _tcn_standalone_bwd(mod, ts, dy):
     part, _ = ops.bn_bwd_reduce(dy, None, False, S, ts.sst, False)
     coef, dg, db = ops.bn_bwd_finalize(part, B, C, B * To * V, ts.sst, mod.bn2)
     dS = ops.bn_bwd_apply(dy, None, False, S, coef, False)
-    dH, g = tcn_core_backward(mod, ts, dS)
+    dH, g, _ = tcn_core_backward(mod, ts, dS)
     g["bn2.weight"], g["bn2.bias"] = dg, db
     return dH, g
 
@@ -994,7 +1009,7 @@ def _convbn_standalone_bwd(mod, s, dy):
     return dx, g
 
 
-GCN_IMPL = (gcn_forward, _gcn_standalone_bwd)
+GCN_IMPL = (gcn_forward, lambda mod, s, dy: gcn_backward(mod, s, dy)[:2])
 TCN_IMPL = (_tcn_standalone_fwd, _tcn_standalone_bwd)
 CONVBN_IMPL = (_convbn_standalone_fwd, _convbn_standalone_bwd)
 UNIT_IMPL = (unit_forward, unit_backward)

@@ -213,26 +213,21 @@ class Model(nn.Module):
 def linked_units(units):
     """Run a chain of TCN_GCN_units with the cross-unit fusions on (what Model.forward
     does for l1..l10): each unit's tail launch also writes the next unit's gathered gcn
-    input, and the next unit's backward makes this unit's bn2 backward partials. The links
-    live only for the duration of the block (a unit used alone runs unfused). Linked units
-    also run their weight-gradient contractions on a side stream, joined before
-    ``backward()`` returns (fused._OffPath)."""
+    input, and the next unit's backward makes this unit's bn2 backward partials and stores
+    its output gradient pre-masked. Linked units also run their weight-gradient contractions
+    on a side stream, joined before ``backward()`` returns (fused._OffPath).
+
+    For the duration of the block each unit carries ONE private attribute, ``_link_pos``: its
+    position in this chain (fused.chain_positions) with a fresh fused._Link to each neighbour.
+    What two units hand each other, forward and backward, travels in those per-call links, so
+    nothing is left on a module and the chain may run several times in one graph."""
+    pos = fused.chain_positions(units)
     try:
-        for u, nxt in zip(units[:-1], units[1:]):
-            u.__dict__["_gather_consumer"] = nxt.gcn1
-            u.__dict__["_next_unit"] = nxt
-        for i, u in enumerate(units):
-            if i or not fused.TAIL_MAIN & 2:
-                u.__dict__["_off_path"] = True
-        # every unit's tanh(Feature_Mask) + 1 in one launch (fused.prepare_masks)
-        fused.prepare_masks([u.gcn1 for u in units])
+        for u, p in zip(units, pos):
+            u.__dict__["_link_pos"] = p
         yield
     finally:
-        for u in units:
-            u.__dict__.pop("_gather_consumer", None)
-            u.__dict__.pop("_next_unit", None)
-            u.__dict__.pop("_off_path", None)
-            u.__dict__.pop("_prev_tail", None)
-            u.__dict__.pop("_prev_out", None)
-            u.gcn1.__dict__.pop("_gather_cache", None)
-            u.gcn1.__dict__.pop("_mask_ready", None)
+        for u, p in zip(units, pos):
+            u.__dict__.pop("_link_pos", None)
+            if p.link_out is not None:   # made for a consumer that did not run
+                p.link_out.take(None)
