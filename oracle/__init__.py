@@ -10,6 +10,9 @@ import this package, and only as the checker / reported CPU baseline. The produc
 * :mod:`oracle.model_oracle` — PyTorch-eager CPU restatement of ``model/shift_gcn.py``
   (``tcn``, ``Shift_tcn``, ``Shift_gcn``, ``TCN_GCN_unit``, ``Model``) on top of the
   numpy shift, plus the reference training-step semantics (``main.py``).
+* :mod:`oracle.stream_ref`   — float64 torch restatements of the streaming kernels
+  (BatchNorm planes, gcn gather / dx-finish, masks, the shift-fused forms).
+* :mod:`oracle.stream_cases` — their test's shape table, inputs and launch-chooser mirrors.
 
 Pinning: see each module's header and DESIGN.md §Oracle.
 """

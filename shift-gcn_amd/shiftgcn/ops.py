@@ -941,11 +941,14 @@ def gcn_dx_finish(dxt, x0, m, add1=None, add2=None, prev=None, add2_mask=None,
     return (dx, part) if prev is None else (dx, part, pp)
 
 
-def mask_grad_finalize(part, mask, B, C, V, out=None):
+def mask_grad_finalize(part, mask, B, C, V, out=None, accumulate=False):
+    """``accumulate`` (needs ``out``): the gradient is added to ``out``."""
+    if accumulate and out is None:
+        raise ValueError("mask_grad_finalize: accumulate needs the tensor to add to (out)")
     dmask = torch.empty_like(mask) if out is None else out
     with _timed("finalize", 0, 4 * part.numel(), mask):
         rc = _lib.load().sgcn_mask_grad_finalize(_ptr(part), _ptr(mask), B, C, V, _ptr(dmask),
-                                                 0, _stream(mask))
+                                                 int(bool(accumulate)), _stream(mask))
     _lib.check(rc, "sgcn_mask_grad_finalize")
     return dmask
 
