@@ -60,8 +60,8 @@ _SIDE = {}
 
 def _side_stream(device):
     s = _SIDE.get(device)
-    if s is None:
-        s = _SIDE[device] = torch.cuda.Stream(device=device)
+    if s is None:   # (setdefault: two replica threads on one device end with one stream)
+        s = _SIDE.setdefault(device, torch.cuda.Stream(device=device))
     return s
 
 
@@ -115,7 +115,10 @@ class _OffPath:
 # tensor, whatever else contributes to the parameter's gradient in the same backward (a
 # regulariser in the loss, a parameter tied across blocks, the model used twice in one
 # graph, an existing ``.grad``). A parameter whose gradient autograd must see during the
-# backward (hooks, ``torch.autograd.grad`` capturing it, ``create_graph``) is not deferred.
+# backward (hooks, ``torch.autograd.grad`` capturing it, ``create_graph``; a non-leaf tensor
+# of an nn.DataParallel replica; any parameter under DistributedDataParallel, whose reducer
+# hooks the AccumulateGrad nodes) is not deferred: its block runs the in-order path, every
+# gradient finished on the current stream and returned to autograd (_defer_ok).
 # --------------------------------------------------------------------------------------
 # Optimizer-only finalizes (position and mask gradients) are deferred to the end of the
 # backward and launched together: one launch per kind instead of one per unit
@@ -163,11 +166,29 @@ def _task(device):
     return t
 
 
-def _defer_ok(params):
-    """Whether the gradients of ``params`` may be written after the block's backward
-    returns: a plain backward that will run their AccumulateGrad (not
+class _Backward(threading.local):
+    """Set by _BlockFunction.backward around a block's ``bwd``. ``in_order``: the block's
+    forward ran inside a DistributedDataParallel forward. DDP's reducer takes each gradient
+    from a C++ hook on the parameter's AccumulateGrad node (invisible to _plain_backward), so
+    every gradient of that block must be a finished tensor handed to autograd, in order.
+    ``params``: the block's parameter tensors as its forward found them (block_params), so
+    the backward does not walk the module again."""
+    in_order = False
+    params = None
+
+
+_BWD = _Backward()
+
+
+def _bwd_params(module):
+    ps = _BWD.params
+    return ps if ps is not None else [p for _, p in block_params(module)]
+
+
+def _plain_backward(params):
+    """Whether this is a plain backward that will run the gradient nodes of ``params`` (not
     ``torch.autograd.grad`` capturing them, not ``backward(inputs=...)`` without them, not
-    ``create_graph``) and nothing that reads a gradient during the backward (tensor hooks,
+    ``create_graph``) with nothing that reads a gradient during the backward (tensor hooks,
     post-accumulate-grad hooks)."""
     if torch.is_grad_enabled():
         return False   # create_graph: AccumulateGrad differentiates through the sum
@@ -182,6 +203,21 @@ def _defer_ok(params):
         except RuntimeError:   # torch.autograd.grad returns p's gradient: not deferred
             return False
     return True
+
+
+def _defer_ok(params):
+    """Whether the gradients of ``params`` may be written after the block's backward
+    returns and accumulated into ``.grad`` by _finish. The ONE place where the reasons for
+    the in-order path meet: the block ran under DistributedDataParallel (_BWD.in_order), a
+    parameter is not a leaf (a DataParallel replica's tensors are outputs of Broadcast:
+    their gradient must flow on through autograd, and they have no ``.grad``), or the
+    backward is not a plain one / something reads a gradient during it (_plain_backward)."""
+    if _BWD.in_order:
+        return False
+    for p in params:
+        if not p.is_leaf:
+            return False
+    return _plain_backward(params)
 
 
 def _accumulate(p, g):
@@ -748,7 +784,7 @@ def _off_path_ok(unit, s: UnitSaved):
     to .grad at the end of the backward, after the join."""
     if not s.off or torch.cuda.is_current_stream_capturing():
         return False
-    if not _defer_ok([p for p in unit.parameters() if p.requires_grad]):
+    if not _defer_ok(_bwd_params(unit)):
         return False
     _task(s.x.device).side = True
     return True
@@ -764,16 +800,16 @@ def _premask_ok(unit, x, off):
     sees the gradient. Not with tensor hooks or ``retain_grad`` on x, not when this backward
     will not run that unit's node, not under ``torch.autograd.grad`` /
     ``backward(inputs=...)`` (which may capture x's gradient: told from this unit's own
-    parameters, whose AccumulateGrad a plain backward runs, the query _defer_ok makes; a unit
-    without trainable parameters cannot tell and does not mask), ``create_graph`` or a
-    hipGraph capture."""
+    parameters, whose gradient nodes a plain backward runs, the query _plain_backward makes;
+    a unit without trainable parameters cannot tell and does not mask), ``create_graph`` or
+    a hipGraph capture."""
     if not PREMASK or torch.cuda.is_current_stream_capturing():
         return False
     if getattr(x, "_backward_hooks", None) or x.retains_grad or x.grad_fn is None:
         return False
     if not off:   # (off: _off_path_ok has asked _defer_ok about every parameter)
-        params = [p for p in unit.parameters() if p.requires_grad]
-        if not params or not _defer_ok(params):
+        params = _bwd_params(unit)
+        if not params or not _plain_backward(params):
             return False
     try:
         return bool(torch._C._will_engine_execute_node(x.grad_fn))
@@ -894,12 +930,43 @@ ASYNC_DW = int(os.environ.get("SGCN_ASYNC_DW", "1"))
 PREMASK = int(os.environ.get("SGCN_PREMASK", "1"))
 
 
-def trainable(module):
-    return [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+def block_params(module):
+    """[(dotted name, tensor)] of the block's trainable parameters, in ``named_parameters()``
+    order: the keys of the gradient dict its ``bwd`` returns. A replica made by
+    ``torch.nn.parallel.replicate`` (nn.DataParallel) has an empty ``_parameters``: its
+    parameters are plain attributes, non-leaf outputs of Broadcast, listed per submodule in
+    ``_former_parameters`` in the master's order. Those are taken under the master's names, so
+    their gradients flow back through autograd to the master's parameters."""
+    if not module.__dict__.get("_is_replica"):
+        return [(n, p) for n, p in module.named_parameters() if p.requires_grad]
+    out, seen = [], set()
+    for prefix, m in module.named_modules():
+        for k, p in m.__dict__.get("_former_parameters", {}).items():
+            if p is None or not p.requires_grad or id(p) in seen:
+                continue
+            seen.add(id(p))   # (a tied parameter once, under its first name)
+            out.append((prefix + "." + k if prefix else k, p))
+    return out
+
+
+_ddp_active = getattr(torch.nn.parallel.DistributedDataParallel, "_get_active_ddp_module",
+                      lambda: None)
+
+
+def _check_ddp_slots(module, params):
+    """DistributedDataParallel reduces the gradients itself; with dist.GradAllReduce's bucket
+    registered for the same parameters they would be reduced twice."""
+    for p in params:
+        if p in ops._GRAD_SLOTS:
+            raise RuntimeError(
+                f"{type(module).__name__}: the model is wrapped in DistributedDataParallel "
+                "while shiftgcn.dist.GradAllReduce holds its parameters: the gradients would "
+                "be reduced twice. Use one of them (GradAllReduce.close() releases the bucket)")
 
 
 class _BlockFunction(torch.autograd.Function):
-    """Generic Function: ``fwd(module, x, training) -> (y, saved)`` and
+    """``apply(impl, module, names, x, *params)`` with (names, params) = block_params(module).
+    Generic Function: ``fwd(module, x, training) -> (y, saved)`` and
     ``bwd(module, saved, dy) -> (dx, {param_name: grad})``.
 
     The block's input and output are registered with ``save_for_backward`` so autograd's
@@ -910,13 +977,17 @@ class _BlockFunction(torch.autograd.Function):
     backward; a second backward through the same graph raises a clear error."""
 
     @staticmethod
-    def forward(ctx, impl, module, x, *params):
+    def forward(ctx, impl, module, names, x, *params):
+        # (names, params: the module's block_params, walked once per call by run_block)
         fwd, bwd = impl
         training = module.training
+        ctx.names, ctx.params = names, params
+        # inside a DistributedDataParallel forward: the backward runs in order (_Backward)
+        ctx.ddp = _ddp_active() is not None
+        if ctx.ddp:
+            _check_ddp_slots(module, ctx.params)
         y, saved = fwd(module, x.contiguous(), training)
         ctx.impl, ctx.module, ctx.saved, ctx.training = impl, module, saved, training
-        tr = trainable(module)
-        ctx.names, ctx.params = [n for n, _ in tr], [p for _, p in tr]
         ctx.save_for_backward(x, y)
         return y
 
@@ -932,7 +1003,12 @@ class _BlockFunction(torch.autograd.Function):
                 "backward (retain_graph=True / double backward is not supported)")
         _, bwd = ctx.impl
         dyp = _unit_dy_planes(ctx, dy)
-        dx, grads = bwd(ctx.module, ctx.saved, dy.contiguous() if dyp is None else dyp)
+        was = _BWD.in_order, _BWD.params
+        _BWD.in_order, _BWD.params = ctx.ddp, ctx.params
+        try:
+            dx, grads = bwd(ctx.module, ctx.saved, dy.contiguous() if dyp is None else dyp)
+        finally:
+            _BWD.in_order, _BWD.params = was
         ctx.saved = None
         out = []
         for n, p in zip(ctx.names, ctx.params):
@@ -941,7 +1017,7 @@ class _BlockFunction(torch.autograd.Function):
                 _task(g.t.device).grads.append((p, g.t))
                 g = None
             out.append(g)
-        return (None, None, dx) + tuple(out)
+        return (None, None, None, dx) + tuple(out)
 
 
 def _unit_dy_planes(ctx, dy):
@@ -966,12 +1042,11 @@ _INFER = _InferFlag()
 
 
 def run_block(impl, module, x):
-    params = [p for _, p in trainable(module)]
+    tr = block_params(module)
     prev = _INFER.active
-    _INFER.active = not (torch.is_grad_enabled() and
-                         (x.requires_grad or any(p.requires_grad for p in params)))
+    _INFER.active = not (torch.is_grad_enabled() and (x.requires_grad or bool(tr)))
     try:
-        return _BlockFunction.apply(impl, module, x, *params)
+        return _BlockFunction.apply(impl, module, [n for n, _ in tr], x, *[p for _, p in tr])
     finally:
         _INFER.active = prev
 

@@ -159,7 +159,10 @@ def release_grad_slots(params):
 
 def grad_like(p):
     """Output tensor for p's gradient: its bucket slot while p.grad is None and the slot was
-    not handed out yet since the last release, else a new tensor like p."""
+    not handed out yet since the last release, else a new tensor like p. A non-leaf p (a
+    DataParallel replica's tensor) has neither a slot nor a ``.grad``: always a new tensor."""
+    if not p.is_leaf:
+        return torch.empty_like(p)
     if p.grad is None and p not in _SLOT_TAKEN:
         v = grad_slot(p)
         if v is not None:
