@@ -194,7 +194,8 @@ int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
  * rsign = +1 is Shift_gcn's shift_in gather x[:, (v+c) mod V] (shift_gcn.py:108-112,127);
  * as an OUTPUT mapping rsign = +1 stores y[d, t, v] at ((v+d) mod V), which is the
  * shift_out gather z[v] = y[(v-d) mod V] (shift_gcn.py:114-118,136). tstride = 2 is the
- * strided residual conv (shift_gcn.py:35-36). */
+ * strided residual conv (shift_gcn.py:35-36). rsign is -1, 0 or +1 and tstride >= 1 on
+ * every operand (else SGCN_EINVAL). */
 
 /* Y[b][m][out(n,m)] (+)= act( sum_k A[m][k] * X'(b,k,n) + bias[m] ),  n < T*V
  * A = w: w_mcontig ? w[k*M + m] : w[m*K + k];  X'(b,k,n) = X(b,k,n) * (mask ? mask[v*K+k] : 1)

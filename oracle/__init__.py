@@ -13,6 +13,10 @@ import this package, and only as the checker / reported CPU baseline. The produc
 * :mod:`oracle.stream_ref`   — float64 torch restatements of the streaming kernels
   (BatchNorm planes, gcn gather / dx-finish, masks, the shift-fused forms).
 * :mod:`oracle.stream_cases` — their test's shape table, inputs and launch-chooser mirrors.
+* :mod:`oracle.pw_ref`       — float64 torch restatements of the pointwise contractions
+  (``sgcn_pw_fwd`` / ``sgcn_pw_dw`` / ``sgcn_pw_fwd_tshift``) through the header's plane
+  addressing formula.
+* :mod:`oracle.pw_cases`     — their test's shape tables and host-chooser mirrors.
 
 Pinning: see each module's header and DESIGN.md §Oracle.
 """

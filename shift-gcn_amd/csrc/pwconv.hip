@@ -1626,6 +1626,7 @@ int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_t
                size_t ws_bytes, int B, int M, int Nc, int T, int V, void* stream) {
   SGCN_REQUIRE(B > 0 && M > 0 && Nc > 0 && T > 0 && V > 0 && V < 32768);
   SGCN_REQUIRE(g && x && dw && ws && g_tstride >= 1 && x_tstride >= 1);
+  SGCN_REQUIRE(g_rsign >= -1 && g_rsign <= 1 && x_rsign >= -1 && x_rsign <= 1);
   SGCN_REQUIRE(!mask || V <= kMaskMaxV);
   SGCN_REQUIRE(ws_bytes >= sgcn_pw_dw_ws_bytes(B, M, Nc, T, V));
   SGCN_REQUIRE(g_cstride * (long long)M < (1LL << 31) && x_cstride * (long long)Nc < (1LL << 31));

@@ -546,12 +546,18 @@ def tshift_bwd_bnin(dy, y, s, coef, inp, xpos, ypos, defer_pos=False, pos_out=No
 # --------------------------------------------------------------------------------------
 class PlaneView:
     """Plane-operand addressing of include/shiftgcn.h: element (b, ch, n = t*V + v) at
-    ``t.data[b*bstride + ch*cstride + (t*tstride)*V + (v + rsign*ch) mod V]``."""
+    ``t.data[b*bstride + ch*cstride + (t*tstride)*V + (v + rsign*ch) mod V]``. ``t`` is
+    (B, C, T', V) with dense rows; its batch and channel strides are taken as they are, so a
+    batch / channel (/ leading-row) slice of a larger tensor is addressed in place."""
 
     __slots__ = ("t", "bstride", "cstride", "tstride", "rsign")
 
     def __init__(self, t, tstride=1, rsign=0):
-        check_input(t, "plane operand")
+        if t.is_cuda and t.dtype == _F32 and t.dim() == 4 and t.numel() and \
+                t.stride(3) == 1 and t.stride(2) == t.shape[3]:
+            pass    # a slice whose planes keep the row pitch V
+        else:
+            check_input(t, "plane operand")
         self.t = t
         self.bstride = t.stride(0)
         self.cstride = t.stride(1)
@@ -657,7 +663,7 @@ def pw_fwd_tshift(w, bias, x: PlaneView, xpos, ypos, st, out: PlaneView, M, K, T
     sc = st.scale if st is not None else None
     sh = st.shift if st is not None else None
     if x_shifted is not None:
-        check_input(x_shifted, "x_shifted")
+        PlaneView(x_shifted)
         if x_shifted.shape != x.t.shape or x_shifted.stride() != x.t.stride():
             raise ValueError("x_shifted must have the layout of x")
     nbx = 4.0 * P * (M + K * (2 if x_shifted is not None else 1))

@@ -26,6 +26,9 @@ CASES = [
     (2, 256, 256, 9, 25),
     (3, 64, 64, 11, 33),
     (1, 128, 256, 7, 25),
+    (2, 100, 37, 9, 25),        # ragged K: operand rows clamped to K - 1
+    (2, 37, 130, 7, 33),        # ragged K and M
+    (1, 40, 300, 5, 25),        # M > 256: two M-blocks form the side output
 ]
 
 
