@@ -1202,9 +1202,10 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
     for (int k = 0; k < 6; ++k) lds[k * NT + tid] = a6[k];
     __syncthreads();
     // one thread per (sum k, joint w): GR dependent LDS reads each instead of 6*GR
-    if (tid < 6 * W) {
+    // (a second round where 6 * W > NT: 256 threads at W >= 43)
+    for (int i = tid; i < 6 * W; i += NT) {
       const size_t np = (size_t)gridDim.x * W;
-      const int k = tid / W, wk = tid - k * W;
+      const int k = i / W, wk = i - k * W;
       float sum = 0.f;
       for (int gg = 0; gg < GR; ++gg) sum += lds[k * NT + gg * W + wk];
       gzpart[k * np + (size_t)plane * W + wk] = sum;
