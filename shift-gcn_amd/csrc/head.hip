@@ -28,6 +28,19 @@ __device__ __forceinline__ int clip_col(int j, int V, int M) {
 
 // part[n][f] = {mean, M2} over t of clip column (m, v) of channel c (shifted sums, as
 // bn.hip moments_kernel). Grid N*C; bytes: 4 per clip element.
+//
+// The sums are shifted by the column's first frame k0: a = sum (x - k0), q = sum (x - k0)^2,
+// M2 = q - a*a/T. That costs a factor q/M2 = 1 + (k0 - mean)^2/var in M2's relative error.
+// A frame drawn from the column's own spread keeps the factor small, and the result stands.
+// Raw skeleton input need not: a joint missing (0) or an outlier in the first frame and
+// nearly still afterwards puts the factor near T (M2 off by 1e-4 .. 7e-4 at T = 300;
+// DESIGN.md "Head, finalize and SGD reference tests"). The factor is known once the sums
+// are: a column above kHCond (less for long per-thread sums, whose rounding grows with the
+// rows each thread adds) is summed again about the mean just found, from cache (an (n, c)
+// slab is T*V*M*4 bytes, 60 KB at NTU).
+constexpr float kHCond = 20.f;       // q/M2 of a pivot 4.4 sigma from the mean
+constexpr float kHCondRows = 1200.f; // kHCond * 60 rows per thread (NTU: T = 300, G = 5)
+
 __global__ __launch_bounds__(kHT) void head_moments_kernel(const float* __restrict__ x,
                                                            float2* __restrict__ part, int C,
                                                            int T, int V, int M) {
@@ -39,6 +52,8 @@ __global__ __launch_bounds__(kHT) void head_moments_kernel(const float* __restri
   const int i = threadIdx.x;
   const int Jc = min(J, kHT), G = kHT / Jc;
   const int jl = i % Jc, r = i / Jc;
+  const float nT = (float)T;
+  const float cond = fminf(kHCond, kHCondRows / (float)((T + G - 1) / G));
   for (int jb = 0; jb < J; jb += Jc) {
     const int j = jb + jl;
     const bool act = r < G && j < J;
@@ -61,12 +76,42 @@ __global__ __launch_bounds__(kHT) void head_moments_kernel(const float* __restri
     s1[i] = a;
     s2[i] = q;
     __syncthreads();
+    // every row group of a column merges the same values in the same order, so all of them
+    // decide alike
+    float ta = 0.f, tq = 0.f;
+    for (int g = 0; g < G; ++g) { ta += s1[g * Jc + jl]; tq += s2[g * Jc + jl]; }
+    float mean = k0 + ta / nT, m2 = tq - ta * ta / nT;
+    const bool again = act && tq > cond * m2;
+    if (__syncthreads_or(again)) {   // block-uniform; the merge above has read s1 and s2
+      a = 0.f;
+      q = 0.f;
+      if (again) {
+        for (int t0 = r; t0 < T; t0 += G * kHU) {
+          float xv[kHU];
+#pragma unroll
+          for (int u = 0; u < kHU; ++u) xv[u] = xs[(size_t)min(t0 + u * G, T - 1) * J + col];
+#pragma unroll
+          for (int u = 0; u < kHU; ++u) {
+            const float d = (t0 + u * G < T) ? xv[u] - mean : 0.f;
+            a += d;
+            q += d * d;
+          }
+        }
+      }
+      s1[i] = a;
+      s2[i] = q;
+      __syncthreads();
+      if (again) {   // a corrects the rounding of the mean
+        ta = 0.f;
+        tq = 0.f;
+        for (int g = 0; g < G; ++g) { ta += s1[g * Jc + jl]; tq += s2[g * Jc + jl]; }
+        mean += ta / nT;
+        m2 = tq - ta * ta / nT;
+      }
+    }
     if (i < Jc && jb + i < J) {
-      float ta = 0.f, tq = 0.f;
-      for (int g = 0; g < G; ++g) { ta += s1[g * Jc + i]; tq += s2[g * Jc + i]; }
       const int jj = jb + i, m = jj / V, v = jj - m * V;
-      const float nT = (float)T;
-      part[(size_t)n * F + (m * V + v) * C + c] = make_float2(k0 + ta / nT, tq - ta * ta / nT);
+      part[(size_t)n * F + (m * V + v) * C + c] = make_float2(mean, m2);
     }
     __syncthreads();
   }
