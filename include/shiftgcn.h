@@ -22,7 +22,7 @@ extern "C" {
 #endif
 
 #define SGCN_EINVAL (-22)
-#define SGCN_ABI_VERSION 24
+#define SGCN_ABI_VERSION 25
 /* Set in sgcn_abi_version()'s value by a diagnostic build (SGCN_PW_DIAG, SGCN_PW_STAMPS,
  * SGCN_DIAG_*: timing probes whose results are WRONG, `make diag` only); the Python loader
  * refuses such a library. */
@@ -48,7 +48,10 @@ extern "C" {
  * sgcn_gcn_dx_finish takes flags (SGCN_DXF_MASK_DX: dx stored as dx * (x0 > 0);
  * SGCN_DXF_ADD2_PLANE: add2 is (B*C)); sgcn_tshift_bwd_bnin accepts y = NULL (dy already
  * masked) and takes dy_plane; sgcn_bn_bwd_reduce takes dy_plane; sgcn_pool_bwd_planes (the
- * pool gradient's (N*M, C) plane values). */
+ * pool gradient's (N*M, C) plane values).
+ * 25: the sequence pipeline: sgcn_window_normalize (every sliding window of a landmark
+ * sequence cut, padded and pre-normalised on the device) and sgcn_window_aggregate (window
+ * scores averaged per frame). */
 int sgcn_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -387,6 +390,56 @@ int sgcn_modalities(const float* joint, const int* parent, float* out_joint, flo
                     float* out_joint_motion, float* out_bone_motion, const float* scale,
                     const float* shift, int planes, int N, int C, int T, int V, int M,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Sequence pipeline (config 4: a whole landmark sequence scored on the device)
+ * ---------------------------------------------------------------------------------- */
+/* Largest W*M of sgcn_window_normalize (its per-window frame maps live in LDS). */
+#define SGCN_SEQ_MAX_WM 2048
+
+/* Replaces `create_sliding_windows` (inference_pipeline.py:252-281) followed by
+ * `pre_normalize` (:167-245 = data_gen/preprocess.py:8-91) for every window in one launch.
+ * seq  : (3, T, V, M) landmark sequence;  table: (n_windows, 2) int32 {start, num_real},
+ *   window n covers frames [start, start + num_real), num_real <= W;
+ * out  : (n_windows, 3, W, V, M), the layout the ensemble takes.
+ * z_bottom/z_top, x_right/x_left, center_a/center_b: the joints of pre_normalization's
+ *   zaxis, xaxis and center_joint; center_b = -1 for a single centre joint. NTU:
+ *   z = [0, 1], x = [8, 4], centre = 1; MediaPipe: z = [23, 11], x = [12, 11],
+ *   centre = [23, 24].
+ * stages: bit mask, 1 = pad, 2 = centre, 4 = rotate; 7 is pre_normalize, the partial values
+ *   are the exact prefixes of it (0 = the zero-padded window alone).
+ * Per window and person m, in closed form:
+ *   1. raw[t] = seq[:, start + t] for t < num_real, else 0. A frame is null when all of its
+ *      V*3 values are 0. (The reference tests `frame.sum() == 0`; the two differ only when
+ *      the values of a frame happen to cancel.)
+ *   2. An all-null person gives zeros. When raw[0] is null, the non-null frames are moved
+ *      to the front, in order.
+ *   3. L = start of the trailing run of null frames; if 0 < L < W, frame t >= L becomes
+ *      frame (t - L) mod L. Null frames before L stay zero.
+ *   4. (2) centre[t] = person 0's padded joint center_a at frame t, or (a + b) / 2 in
+ *      float32; p = (p - centre[t]) * ((x + y) + z != 0), the mask in float32 per joint.
+ *   5. (4) Z then X. v = joint[z_top] - joint[z_bottom] of person 0, frame 0, in float32;
+ *      axis v x (0,0,1); angle arccos(clip(v_z / |v|)) with v / |v| in float32 and the rest
+ *      in float64 (0 when sum|v| < 1e-6); the Rodrigues matrix of rotation.py:5-20
+ *      (identity when sum|axis| < 1e-6 or |angle| < 1e-6); every joint with (x + y) + z != 0
+ *      is multiplied by it in float64 and rounded to float32. Then the same with
+ *      v = joint[x_right] - joint[x_left] of the Z-rotated frame 0 and the axis (1,0,0).
+ * Steps 1-4 are bit-exact with the reference; step 5 differs from it by float32 rounding
+ * of |v| and the device's acos/sin/cos. NaN or Inf inputs are undefined.
+ * Requires W*M <= SGCN_SEQ_MAX_WM and every joint index < V (EINVAL otherwise);
+ * n_windows == 0 returns 0 without a launch. The table lives on the device, so its rows
+ * cannot be checked here: a row is clamped to the sequence and to W (it never reads or
+ * writes out of bounds); shiftgcn.pipeline checks a host table before it uploads it. */
+int sgcn_window_normalize(const float* seq, const int* table, float* out, int n_windows, int T,
+                          int V, int M, int W, int z_bottom, int z_top, int x_right,
+                          int x_left, int center_a, int center_b, int stages, void* stream);
+
+/* `aggregate_per_frame` (inference_pipeline.py:377-386) in float64: per_frame[f] = (sum of
+ * scores[i] over the windows with start <= f < start + num_real, added in table order) /
+ * max(count, 1): bit-identical to the reference for the same scores.
+ * scores: (n_windows) float64;  per_frame: (total_frames) float64. */
+int sgcn_window_aggregate(const double* scores, const int* table, double* per_frame,
+                          int n_windows, int total_frames, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Model head / tail of the training step (shift_gcn.py:193-216)

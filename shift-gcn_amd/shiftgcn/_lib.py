@@ -17,8 +17,9 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 # same-box A/B of two builds (tuning only, e.g. tools/ab_lib.sh): another in-tree build of
 # the same ABI
 LIB_PATH = os.environ.get("SGCN_LIB_PATH", LIB_PATH)
-ABI_VERSION = 24
+ABI_VERSION = 25
 BATCH_MAX = 32            # include/shiftgcn.h SGCN_BATCH_MAX
+SEQ_MAX_WM = 2048         # include/shiftgcn.h SGCN_SEQ_MAX_WM
 ABI_DIAG_FLAG = 0x10000   # include/shiftgcn.h SGCN_ABI_DIAG_FLAG: a diagnostic build
 EINVAL = -22
 
@@ -76,6 +77,9 @@ SIGNATURES = {
                                   _I, _I, _I, _P]),
     "sgcn_mask_grad_finalize": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
     "sgcn_modalities": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "sgcn_window_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                                   _P]),
+    "sgcn_window_aggregate": (_I, [_P, _P, _P, _I, _I, _P]),
     "sgcn_tshift_bwd_gbn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     "sgcn_bn_bwd_finalize_gbn": (_I, [_P, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I,
