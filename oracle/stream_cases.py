@@ -5,18 +5,23 @@ ONLY).
 ``tests/test_gpu_stream_ref.py`` runs every op over :data:`TABLE` (+ :data:`SHIFT_EXTRA` for
 the shift-fused ops); ``tests/test_oracle_stream.py`` checks, without a GPU, that those
 shapes reach every launch form a plane CAN reach, by enumerating all planes through the
-mirrors below. Each mirror restates one C++ host function; when a chooser changes, its
-mirror (and, if a new form appears, the table) changes with it — the coverage test fails
-until the table reaches the new form.
+mirrors below. Each mirror restates one host function of
+``shift-gcn_amd/csrc/launch_forms.hpp`` (the entry points call those, so they are the
+library's decision); ``tests/test_launch_forms.py`` compiles that header into a host program
+and compares it with the mirrors on every plane. When a chooser changes, its mirror (and, if
+a new form appears, the table) changes with it — the coverage test fails until the table
+reaches the new form.
 
-Forms no plane can reach (instantiated, never launched; kept — removing them is not this
-table's business):
+Forms no plane can reach. They are no longer built: a launcher instantiates its form list in
+``launch_forms.hpp``, which the same test holds equal to the forms the chooser returns (a
+form outside the list is refused with SGCN_EINVAL, never mapped to another):
 
 * BatchNorm plane kernels and ``gcn_dx_finish_ja_kernel``: 512 x 8 and 512 x 16. 512
   threads are chosen only above 8,192 floats, and (512 / V) * V <= 512 lanes then hold at
   least 17 elements each.
 * padded forward (``tshift_fwd_pad_kernel`` behind ``sgcn_tshift_fwd_pre`` / ``_tail``):
-  512 x 8, 512 x 12 and 512 x 16, for the same reason (512 threads above 8,192 floats).
+  512 x 8, 512 x 12 and 512 x 16, for the same reason (512 threads above 8,192 floats);
+  behind ``sgcn_tshift_fwd`` also 256 x 12 and 256 x 20 (12 and 20 are 512-thread counts).
 * stride-1 backward behind ``sgcn_tshift_bwd_bnin``: 512 x 8 (512 threads above 4,096
   floats: at least 9 per lane) and 256 x 32 (256 threads up to 4,096 floats; the
   narrowest joint-aligned stride of any V <= 64 is 208 lanes (V = 52): at most 20 per
@@ -27,13 +32,13 @@ from __future__ import annotations
 # --------------------------------------------------------------------------------------
 # mirrors of the launch choosers
 # --------------------------------------------------------------------------------------
-K_JA_SPLIT = 8192        # bn.hip kJaSplit
-K_FWD_LDS_MAX = 8192     # tshift.hip kFwdLdsMax
-K_FWD_LDS_MAX2 = 16384   # tshift.hip kFwdLdsMax2
-K_BWD_LDS_MAX = 16384    # tshift.hip kBwdLdsMax
-K_PAD_ROWS = 4           # tshift.hip kPadRows
-K_BNIN_SPLIT = 4096      # tshift.hip sgcn_tshift_bwd_bnin: `H * W <= 4096 ? 256 : 512`
-K_LDS_BYTES = 65536      # tshift.hip kRaLdsMax / pad_fwd_lpt's 64 KiB
+K_JA_SPLIT = 8192        # launch_forms.hpp kJaSplit
+K_FWD_LDS_MAX = 8192     # launch_forms.hpp kFwdLdsMax
+K_FWD_LDS_MAX2 = 16384   # launch_forms.hpp kFwdLdsMax2
+K_BWD_LDS_MAX = 16384    # launch_forms.hpp kBwdLdsMax
+K_PAD_ROWS = 4           # launch_forms.hpp kPadRows
+K_BNIN_SPLIT = 4096      # launch_forms.hpp kBninSplit
+K_LDS_BYTES = 65536      # launch_forms.hpp kRaLdsMax / pad_fwd_lpt's 64 KiB
 K_PLANE_V_MAX = 256      # bn.hip SGCN_PLANE_CHECK: V <= kThreads
 
 
@@ -42,7 +47,7 @@ def _bucket(per):
 
 
 def ja_lpt(T, V, nt):
-    """bn.hip ``ja_lpt``."""
+    """launch_forms.hpp ``ja_lpt``."""
     if V > 64:
         return 0
     ntj = (nt // V) * V
@@ -51,7 +56,7 @@ def ja_lpt(T, V, nt):
 
 def bn_form(T, V):
     """Launch form of sgcn_moments / sgcn_bn_apply / sgcn_bn_bwd_reduce / sgcn_bn_bwd_apply /
-    sgcn_gcn_dx_finish (bn.hip: ``nt = T * V <= kJaSplit ? kThreads : 512`` then ``ja_lpt``):
+    sgcn_gcn_dx_finish (launch_forms.hpp ``bn_form``):
     ("ja", threads, per-thread), "loop" (the looping kernels) or "refuse" (SGCN_PLANE_CHECK)."""
     if V > K_PLANE_V_MAX:
         return "refuse"
@@ -61,18 +66,18 @@ def bn_form(T, V):
 
 
 def ra_pad_floats(H, W):
-    """tshift.hip ``ra_pad_floats``."""
+    """launch_forms.hpp ``ra_pad_floats``."""
     return (H + 2 * K_PAD_ROWS) * (W + 2)
 
 
 def pad_lds_fits(H, W):
-    """The pad-LDS limit of tshift.hip ``pad_fwd_lpt`` / ``launch_ra`` (``ra_lds_bytes``
-    without GBN): the padded plane + one spare float within 64 KiB."""
+    """The pad-LDS limit of launch_forms.hpp ``pad_fwd_lpt`` / ``ra_lds_bytes`` (without
+    GBN): the padded plane + one spare float within 64 KiB."""
     return (ra_pad_floats(H, W) + 1) * 4 <= K_LDS_BYTES
 
 
 def pad_fwd_lpt(H, W, nt):
-    """tshift.hip ``pad_fwd_lpt``."""
+    """launch_forms.hpp ``pad_fwd_lpt``."""
     if W > 64:
         return 0
     ntj = (nt // W) * W
@@ -86,14 +91,14 @@ def pad_fwd_lpt(H, W, nt):
 
 
 def pick_lpt(n, nt):
-    """tshift.hip ``pick_lpt``."""
+    """launch_forms.hpp ``pick_lpt``."""
     per = -(-n // nt)
     return 8 if per <= 8 else 16 if per <= 16 else 32
 
 
 def fwd_form(H, W):
-    """Launch form of sgcn_tshift_fwd_pre / sgcn_tshift_fwd_tail (tshift.hip, the two entry
-    points choose alike): ("pad", threads, per-thread), ("fallback", threads, per-thread)
+    """Launch form of sgcn_tshift_fwd_pre / sgcn_tshift_fwd_tail (launch_forms.hpp
+    ``fwd_fused_form``, where "fallback" is the kind ``lds``): ("pad", threads, per-thread), ("fallback", threads, per-thread)
     (tshift_fwd_pre_kernel / tshift_fwd_tail_kernel) or "refuse" (H * W > kFwdLdsMax2)."""
     n = H * W
     if n > K_FWD_LDS_MAX2 or W > 1024:
@@ -108,7 +113,7 @@ def fwd_form(H, W):
 
 
 def ra_lpt(n, nt, W):
-    """tshift.hip ``ra_lpt``."""
+    """launch_forms.hpp ``ra_lpt``."""
     nte = (nt // W) * W
     if nte <= 0 or W > 64:
         return 0
@@ -121,7 +126,7 @@ def ra_lpt(n, nt, W):
 
 
 def bnin_form(H, W):
-    """Launch form of sgcn_tshift_bwd_bnin (tshift.hip: ``ntb`` then ``launch_ra``):
+    """Launch form of sgcn_tshift_bwd_bnin (launch_forms.hpp ``bnin_form``):
     ("ra", threads, per-thread) or "refuse" (SGCN_EINVAL; ``ops.ra_fits`` is False)."""
     n = H * W
     if n > K_BWD_LDS_MAX:

@@ -4,8 +4,10 @@ of sgcn_tshift_fwd, sgcn_tshift_bwd and sgcn_tshift_bwd_gbn (TEST INFRASTRUCTURE
 ``tests/test_gpu_tshift_ref.py`` runs the three entry points over :data:`TABLE` at stride 1
 and 2 (+ :data:`FWD_ONLY`); ``tests/test_oracle_tshift.py`` checks, without a GPU, that
 those planes reach every launch form a plane CAN reach, by enumerating all planes through
-the mirrors below. Each mirror restates one host function of tshift.hip; the choosers shared
-with the shift-fused entry points come from ``oracle.stream_cases``. Every form stands for
+the mirrors below. Each mirror restates one host function of
+``shift-gcn_amd/csrc/launch_forms.hpp`` (``tshift_fwd_form``, ``bwd_form``, ``gbn_form``;
+``tests/test_launch_forms.py`` compares them with that header on every plane); the choosers
+shared with the shift-fused entry points come from ``oracle.stream_cases``. Every form stands for
 the 4 (forward: affine x stats) or 8 (backward: affine x relu_mask x bn_part) template
 instances behind it, which the GPU test runs on every plane.
 """
@@ -14,14 +16,14 @@ from __future__ import annotations
 from . import stream_cases as sc
 from .stream_cases import pad_fwd_lpt, pad_lds_fits, pick_lpt, ra_lpt
 
-K_THREADS = 256          # tshift.hip kThreads (the global-tap kernels)
-K_BWD_THREADS = 512      # tshift.hip kBwdThreads
-K_RA_SPLIT256 = 8192     # tshift.hip kRaSplit256
-GBD_SPLIT = True         # tshift.hip SGCN_GBD_SPLIT
+K_THREADS = 256          # launch_forms.hpp kThreads (the global-tap kernels)
+K_BWD_THREADS = 512      # launch_forms.hpp kBwdThreads
+K_RA_SPLIT256 = 8192     # launch_forms.hpp kRaSplit256
+GBD_SPLIT = True         # launch_forms.hpp SGCN_GBD_SPLIT
 
 
 def pick_ept(n):
-    """tshift.hip ``pick_ept``."""
+    """launch_forms.hpp ``pick_ept``."""
     per = -(-n // K_THREADS)
     return 8 if per <= 8 else 16 if per <= 16 else 32
 

@@ -14,11 +14,11 @@
 // Chan's formula in double by the finalize kernels. Running stats follow PyTorch
 // (momentum 0.1, unbiased running variance, num_batches_tracked += 1).
 #include "common.hpp"
+#include "dispatch.hpp"
+#include "launch_forms.hpp"
 
 namespace sgcn {
 namespace {
-
-constexpr int kThreads = 256;
 
 constexpr int kU = 4;  // elements in flight per thread per loop trip (all loads clamped)
 
@@ -1185,21 +1185,17 @@ __device__ __forceinline__ void mask_grad_body(const float* __restrict__ part,
 
 using namespace sgcn;
 
-// largest plane the plane-resident kernels run on 256 threads (512 above): at NTU T = 300
-// (7,500 floats) 256 x 30 measured 0.8 % faster per step than 512 x 15 (same box,
-// profiles/r03_bnja/ab_moments_reduce_t256.txt)
-constexpr int kJaSplit = 8192;
-
-// elements per thread of the plane-resident joint-aligned kernels on nt threads; 0 = the
-// plane does not fit (V > 64 or more than 32 per thread): the looping kernels take it
-int ja_lpt(int T, int V, int nt) {
-  if (V > 64) return 0;
-  const int ntj = (nt / V) * V, per = (T * V + ntj - 1) / ntj;
-  return per <= 8 ? 8 : (per <= 16 ? 16 : (per <= 24 ? 24 : (per <= 32 ? 32 : 0)));
-}
-
 #define SGCN_PLANE_CHECK() \
   SGCN_REQUIRE(B >= 0 && C > 0 && T >= 0 && V > 0 && V <= kThreads)
+
+// One launch of a BatchNorm plane kernel: the plane-resident joint-aligned kernel `ja` on
+// bn_form's (threads, elements per thread), else the looping kernel `loop`; `a` are the
+// kernel's flags (dispatch.hpp). False: a flag value outside its set, nothing launched.
+template <class J, class L, class... A>
+static bool launch_plane(int T, int V, J&& ja, L&& loop, A... a) {
+  const LaunchForm f = bn_form(T, V);
+  return f.kind == Kind::ja ? with_form<kJaForms>(f.nt, f.lpt, ja, a...) : with_consts(loop, a...);
+}
 
 extern "C" {
 
@@ -1214,29 +1210,14 @@ int sgcn_moments(const float* x, float* part, int B, int C, int T, int V, int pe
   SGCN_REQUIRE(x && part && T > 0);
   hipStream_t st = (hipStream_t)stream;
   SGCN_REQUIRE(per_joint == 0 || per_joint == 3);
-  {   // plane-resident joint-aligned kernel: V <= 64, <= 32 elements per thread
-    const int nt = T * V <= kJaSplit ? kThreads : 512;
-    const int lpt = ja_lpt(T, V, nt);
-    if (lpt) {
-#define SGCN_MJ(NT, L, PJ)                                                                     \
-  moments_ja_kernel<NT, L, PJ, PJ><<<B * C, NT, 0, st>>>(x, (float2*)part, T, V, C)
-#define SGCN_MJ_L(NT, PJ)                                                                      \
-  do {                                                                                         \
-    if (lpt == 8) SGCN_MJ(NT, 8, PJ); else if (lpt == 16) SGCN_MJ(NT, 16, PJ);                 \
-    else if (lpt == 24) SGCN_MJ(NT, 24, PJ);                                                   \
-    else SGCN_MJ(NT, 32, PJ);                                                                  \
-  } while (0)
-      if (nt == kThreads) { if (per_joint) SGCN_MJ_L(kThreads, true); else SGCN_MJ_L(kThreads, false); }
-      else { if (per_joint) SGCN_MJ_L(512, true); else SGCN_MJ_L(512, false); }
-#undef SGCN_MJ_L
-#undef SGCN_MJ
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (per_joint == 3)
-    moments_kernel<true, true><<<B * C, kThreads, 0, st>>>(x, (float2*)part, T, V, C);
-  else moments_kernel<false><<<B * C, kThreads, 0, st>>>(x, (float2*)part, T, V, C);
+  auto ja = [&](auto NT, auto LPT, auto PJ) {
+    moments_ja_kernel<NT, LPT, PJ, PJ><<<B * C, int(NT), 0, st>>>(x, (float2*)part, T, V, C);
+  };
+  auto loop = [&](auto PJ) {
+    moments_kernel<PJ, PJ><<<B * C, kThreads, 0, st>>>(x, (float2*)part, T, V, C);
+  };
+  const bool ok = launch_plane(T, V, ja, loop, per_joint == 3);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1283,80 +1264,22 @@ int sgcn_bn_apply(const float* x, const float* scale, const float* shift, int pe
   dim3 g(B * C);
   float2* ys = (float2*)y_stats;
   if (per_joint == 3) SGCN_REQUIRE(relu && !y_gathered);
-  {   // plane-resident joint-aligned kernel: V <= 64, <= 32 elements per thread
-    const int nt = T * V <= kJaSplit ? kThreads : 512;
-    const int lpt = ja_lpt(T, V, nt);
-    if (lpt) {
-      const int ox = ys ? 1 : (y_gathered ? 2 : 0);
-#define SGCN_AJ(NT, L, PJ, RS, RL, OX, ZU)                                                     \
-  bn_apply_ja_kernel<NT, L, PJ, RS, RL, OX, ZU><<<g, NT, 0, st>>>(                             \
-      x, scale, shift, r, rscale, rshift, y, ys, gather_m, y_gathered, C, T, V)
-#define SGCN_AJ_L(NT, PJ, RS, RL, OX, ZU)                                                      \
-  do {                                                                                         \
-    if (lpt == 8) SGCN_AJ(NT, 8, PJ, RS, RL, OX, ZU);                                          \
-    else if (lpt == 16) SGCN_AJ(NT, 16, PJ, RS, RL, OX, ZU);                                   \
-    else if (lpt == 24) SGCN_AJ(NT, 24, PJ, RS, RL, OX, ZU);                                   \
-    else SGCN_AJ(NT, 32, PJ, RS, RL, OX, ZU);                                                  \
-  } while (0)
-#define SGCN_AJ_T(PJ, RS, RL, OX, ZU)                                                          \
-  do {                                                                                         \
-    if (nt == kThreads) SGCN_AJ_L(kThreads, PJ, RS, RL, OX, ZU);                               \
-    else SGCN_AJ_L(512, PJ, RS, RL, OX, ZU);                                                   \
-  } while (0)
-#define SGCN_AJ_O(PJ, RS, RL, ZU)                                                              \
-  do {                                                                                         \
-    if (ox == 1) SGCN_AJ_T(PJ, RS, RL, 1, ZU);                                                 \
-    else if (ox == 2) SGCN_AJ_T(PJ, RS, RL, 2, ZU);                                            \
-    else SGCN_AJ_T(PJ, RS, RL, 0, ZU);                                                         \
-  } while (0)
-      if (per_joint == 3) {
-        if (ys) {
-          if (res == 0) SGCN_AJ_T(true, 0, true, 1, true);
-          else if (res == 1) SGCN_AJ_T(true, 1, true, 1, true);
-          else SGCN_AJ_T(true, 2, true, 1, true);
-        } else {
-          if (res == 0) SGCN_AJ_T(true, 0, true, 0, true);
-          else if (res == 1) SGCN_AJ_T(true, 1, true, 0, true);
-          else SGCN_AJ_T(true, 2, true, 0, true);
-        }
-      } else if (relu) {
-        if (res == 0) SGCN_AJ_O(false, 0, true, false);
-        else if (res == 1) SGCN_AJ_O(false, 1, true, false);
-        else SGCN_AJ_O(false, 2, true, false);
-      } else {
-        if (res == 0) SGCN_AJ_O(false, 0, false, false);
-        else if (res == 1) SGCN_AJ_O(false, 1, false, false);
-        else SGCN_AJ_O(false, 2, false, false);
-      }
-#undef SGCN_AJ_O
-#undef SGCN_AJ_T
-#undef SGCN_AJ_L
-#undef SGCN_AJ
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-#define SGCN_APPLY_X(PJ, RS, RL, OX)                                                        \
-  bn_apply_kernel<PJ, RS, RL, OX><<<g, kThreads, 0, st>>>(x, scale, shift, r, rscale, rshift, y, \
-                                                          ys, gather_m, y_gathered, C, T, V)
-#define SGCN_APPLY(PJ, RS, RL)                                                               \
-  (ys ? SGCN_APPLY_X(PJ, RS, RL, 1)                                                          \
-      : (y_gathered ? SGCN_APPLY_X(PJ, RS, RL, 2) : SGCN_APPLY_X(PJ, RS, RL, 0)))
-#define SGCN_APPLY_R(PJ, RL) \
-  if (res == 0) SGCN_APPLY(PJ, 0, RL); else if (res == 1) SGCN_APPLY(PJ, 1, RL); else SGCN_APPLY(PJ, 2, RL)
-  if (per_joint == 3) {   // the Shift_gcn tail on the pre-shift_out contraction output
-#define SGCN_APPLY_ZU(RS)                                                                      \
-  (ys ? bn_apply_kernel<true, RS, true, 1, true><<<g, kThreads, 0, st>>>(                      \
-            x, scale, shift, r, rscale, rshift, y, ys, gather_m, y_gathered, C, T, V)          \
-      : bn_apply_kernel<true, RS, true, 0, true><<<g, kThreads, 0, st>>>(                      \
-            x, scale, shift, r, rscale, rshift, y, ys, gather_m, y_gathered, C, T, V))
-    if (res == 0) SGCN_APPLY_ZU(0); else if (res == 1) SGCN_APPLY_ZU(1); else SGCN_APPLY_ZU(2);
-#undef SGCN_APPLY_ZU
-  }
-  else if (relu) { SGCN_APPLY_R(false, true); } else { SGCN_APPLY_R(false, false); }
-#undef SGCN_APPLY_R
-#undef SGCN_APPLY
-#undef SGCN_APPLY_X
+  // per_joint == 3: the Shift_gcn tail on the pre-shift_out contraction output (ZU)
+  const OneOf<0, 1, 2> rs{res};
+  const int ox = ys ? 1 : (y_gathered ? 2 : 0);
+  auto ja = [&](auto NT, auto LPT, auto PJ, auto RS, auto RL, auto OX) {
+    bn_apply_ja_kernel<NT, LPT, PJ, RS, RL, OX, PJ><<<g, int(NT), 0, st>>>(
+        x, scale, shift, r, rscale, rshift, y, ys, gather_m, y_gathered, C, T, V);
+  };
+  auto loop = [&](auto PJ, auto RS, auto RL, auto OX) {
+    bn_apply_kernel<PJ, RS, RL, OX, PJ><<<g, kThreads, 0, st>>>(
+        x, scale, shift, r, rscale, rshift, y, ys, gather_m, y_gathered, C, T, V);
+  };
+  const bool ok =
+      per_joint == 3
+          ? launch_plane(T, V, ja, loop, Const<true>{}, rs, Const<true>{}, OneOf<0, 1>{ox})
+          : launch_plane(T, V, ja, loop, Const<false>{}, rs, relu != 0, OneOf<0, 1, 2>{ox});
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1376,49 +1299,22 @@ int sgcn_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* x
   dim3 g(B * C);
   const bool rb = r != nullptr;
   if (per_joint == 3) SGCN_REQUIRE(relu);
-  {   // plane-resident joint-aligned kernel: V <= 64, <= 32 elements per thread
-    const int nt = T * V <= kJaSplit ? kThreads : 512;
-    const int lpt = ja_lpt(T, V, nt);
-    if (lpt) {
-#define SGCN_RJ(NT, L, PJ, RL, RB)                                                             \
-  (dy_coef ? bn_bwd_reduce_ja_kernel<NT, L, PJ, RL, RB, true><<<g, NT, 0, st>>>(                \
-                 dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,            \
-                 (float2*)rpart, C, T, V, dyp)                                                 \
-           : bn_bwd_reduce_ja_kernel<NT, L, PJ, RL, RB, false><<<g, NT, 0, st>>>(               \
-                 dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,            \
-                 (float2*)rpart, C, T, V, dyp))
-#define SGCN_RJ_L(NT, PJ, RL, RB)                                                              \
-  do {                                                                                         \
-    if (lpt == 8) SGCN_RJ(NT, 8, PJ, RL, RB); else if (lpt == 16) SGCN_RJ(NT, 16, PJ, RL, RB); \
-    else if (lpt == 24) SGCN_RJ(NT, 24, PJ, RL, RB);                                           \
-    else SGCN_RJ(NT, 32, PJ, RL, RB);                                                          \
-  } while (0)
-#define SGCN_RJ_T(PJ, RL, RB)                                                                  \
-  do { if (nt == kThreads) SGCN_RJ_L(kThreads, PJ, RL, RB); else SGCN_RJ_L(512, PJ, RL, RB); } while (0)
-      if (per_joint == 3) { if (rb) SGCN_RJ_T(true, true, true); else SGCN_RJ_T(true, true, false); }
-      else if (relu) { if (rb) SGCN_RJ_T(false, true, true); else SGCN_RJ_T(false, true, false); }
-      else { if (rb) SGCN_RJ_T(false, false, true); else SGCN_RJ_T(false, false, false); }
-#undef SGCN_RJ_T
-#undef SGCN_RJ_L
-#undef SGCN_RJ
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-#define SGCN_RED(PJ, RL, RB)                                                                \
-  (dy_coef ? bn_bwd_reduce_kernel<PJ, RL, RB, true><<<g, kThreads, 0, st>>>(                   \
-                 dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,           \
-                 (float2*)rpart, C, T, V, dyp)                                                \
-           : bn_bwd_reduce_kernel<PJ, RL, RB, false><<<g, kThreads, 0, st>>>(                  \
-                 dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part,           \
-                 (float2*)rpart, C, T, V, dyp))
-  if (per_joint == 3) {   // x = the pre-shift_out contraction output (see the kernel)
-    if (rb) SGCN_RED(true, true, true); else SGCN_RED(true, true, false);
-  } else {
-    if (relu) { if (rb) SGCN_RED(false, true, true); else SGCN_RED(false, true, false); }
-    else { if (rb) SGCN_RED(false, false, true); else SGCN_RED(false, false, false); }
-  }
-#undef SGCN_RED
+  // per_joint == 3: x = the pre-shift_out contraction output (see the kernels)
+  const bool dyt = dy_coef != nullptr;
+  auto ja = [&](auto NT, auto LPT, auto PJ, auto RL, auto RB, auto DYT) {
+    bn_bwd_reduce_ja_kernel<NT, LPT, PJ, RL, RB, DYT><<<g, int(NT), 0, st>>>(
+        dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part, (float2*)rpart, C, T,
+        V, dyp);
+  };
+  auto loop = [&](auto PJ, auto RL, auto RB, auto DYT) {
+    bn_bwd_reduce_kernel<PJ, RL, RB, DYT><<<g, kThreads, 0, st>>>(
+        dy, y, x, mean, invstd, r, rmean, rinvstd, dy_coef, (float2*)part, (float2*)rpart, C, T,
+        V, dyp);
+  };
+  const bool ok = per_joint == 3
+                      ? launch_plane(T, V, ja, loop, Const<true>{}, Const<true>{}, rb, dyt)
+                      : launch_plane(T, V, ja, loop, Const<false>{}, relu != 0, rb, dyt);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1466,52 +1362,20 @@ int sgcn_bn_bwd_apply(const float* dy, const float* y, int relu, const float* x,
   const int F = per_joint ? C * V : C;
   dim3 g(B * C);
   if (per_joint == 3) SGCN_REQUIRE(relu);
-  {   // plane-resident joint-aligned kernel: V <= 64, <= 32 elements per thread
-    const int nt = T * V <= kJaSplit ? kThreads : 512;
-    const int lpt = ja_lpt(T, V, nt);
-    if (lpt) {
-#define SGCN_BJ(NT, L, PJ, RL, RS)                                                             \
-  (dy_coef ? bn_bwd_apply_ja_kernel<NT, L, PJ, RL, RS, true><<<g, NT, 0, st>>>(                 \
-                 dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V)             \
-           : bn_bwd_apply_ja_kernel<NT, L, PJ, RL, RS, false><<<g, NT, 0, st>>>(                \
-                 dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V))
-#define SGCN_BJ_L(NT, PJ, RL, RS)                                                              \
-  do {                                                                                         \
-    if (lpt == 8) SGCN_BJ(NT, 8, PJ, RL, RS);                                                  \
-    else if (lpt == 16) SGCN_BJ(NT, 16, PJ, RL, RS);                                           \
-    else if (lpt == 24) SGCN_BJ(NT, 24, PJ, RL, RS);                                           \
-    else SGCN_BJ(NT, 32, PJ, RL, RS);                                                          \
-  } while (0)
-#define SGCN_BJ_T(PJ, RL, RS)                                                                  \
-  do { if (nt == kThreads) SGCN_BJ_L(kThreads, PJ, RL, RS); else SGCN_BJ_L(512, PJ, RL, RS); } while (0)
-#define SGCN_BJ_R(PJ, RL)                                                                      \
-  do {                                                                                         \
-    if (res == 0) SGCN_BJ_T(PJ, RL, 0);                                                        \
-    else if (res == 1) SGCN_BJ_T(PJ, RL, 1);                                                   \
-    else SGCN_BJ_T(PJ, RL, 2);                                                                 \
-  } while (0)
-      if (per_joint == 3) SGCN_BJ_R(3, true);
-      else if (relu) SGCN_BJ_R(0, true);
-      else SGCN_BJ_R(0, false);
-#undef SGCN_BJ_R
-#undef SGCN_BJ_T
-#undef SGCN_BJ_L
-#undef SGCN_BJ
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-#define SGCN_BA(PJ, RL, RS)                                                                   \
-  (dy_coef ? bn_bwd_apply_kernel<PJ, RL, RS, true><<<g, kThreads, 0, st>>>(                      \
-                 dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V)                      \
-           : bn_bwd_apply_kernel<PJ, RL, RS, false><<<g, kThreads, 0, st>>>(                     \
-                 dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V))
-#define SGCN_BA_R(PJ, RL) \
-  if (res == 0) SGCN_BA(PJ, RL, 0); else if (res == 1) SGCN_BA(PJ, RL, 1); else SGCN_BA(PJ, RL, 2)
-  if (per_joint == 3) { SGCN_BA_R(3, true); }
-  else if (relu) { SGCN_BA_R(0, true); } else { SGCN_BA_R(0, false); }
-#undef SGCN_BA_R
-#undef SGCN_BA
+  const OneOf<0, 1, 2> rs{res};
+  const bool dyt = dy_coef != nullptr;
+  auto ja = [&](auto NT, auto LPT, auto PJM, auto RL, auto RS, auto DYT) {
+    bn_bwd_apply_ja_kernel<NT, LPT, PJM, RL, RS, DYT><<<g, int(NT), 0, st>>>(
+        dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V);
+  };
+  auto loop = [&](auto PJM, auto RL, auto RS, auto DYT) {
+    bn_bwd_apply_kernel<PJM, RL, RS, DYT><<<g, kThreads, 0, st>>>(
+        dy, y, x, coef, F, r, rcoef, C, dy_coef, dx, dr, C, T, V);
+  };
+  const bool ok = per_joint == 3
+                      ? launch_plane(T, V, ja, loop, Const<3>{}, Const<true>{}, rs, dyt)
+                      : launch_plane(T, V, ja, loop, Const<0>{}, relu != 0, rs, dyt);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1591,63 +1455,25 @@ int sgcn_gcn_dx_finish(const float* dxt, const float* x0, const float* m, const 
   hipStream_t st = (hipStream_t)stream;
   float2* pp = (float2*)prev_part;
   if (add2_mask) SGCN_REQUIRE(add1);
-  {   // plane-resident joint-aligned kernel: V <= 64, <= 32 elements per thread
-    // (the identity-unit form holds ~200 VGPRs at 256 x 32 — two workgroups per CU — but
-    // 512 x 16, twice the waves, measured 2 % slower: profiles/r05_ar/ab_dx_finish_512.txt)
-    const int nt = T * V <= kJaSplit ? kThreads : 512;
-    const int lpt = ja_lpt(T, V, nt);
-    if (lpt) {
-#define SGCN_FJ(NT, L, A1, A2, PT, AM)                                                         \
-  gcn_dx_finish_ja_kernel<NT, L, A1, A2, PT, AM><<<B * C, NT, 0, st>>>(                        \
-      dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,     \
-      add2_mask, flags)
-#define SGCN_FJ_L(NT, A1, A2, PT, AM)                                                          \
-  do {                                                                                         \
-    if (lpt == 8) SGCN_FJ(NT, 8, A1, A2, PT, AM);                                              \
-    else if (lpt == 16) SGCN_FJ(NT, 16, A1, A2, PT, AM);                                       \
-    else if (lpt == 24) SGCN_FJ(NT, 24, A1, A2, PT, AM);                                       \
-    else SGCN_FJ(NT, 32, A1, A2, PT, AM);                                                      \
-  } while (0)
-#define SGCN_FJ_T(A1, A2, PT, AM)                                                              \
-  do { if (nt == kThreads) SGCN_FJ_L(kThreads, A1, A2, PT, AM); else SGCN_FJ_L(512, A1, A2, PT, AM); } while (0)
-#define SGCN_FJ_P(A1, A2, AM)                                                                  \
-  do { if (pp) SGCN_FJ_T(A1, A2, true, AM); else SGCN_FJ_T(A1, A2, false, AM); } while (0)
-      if (add2_mask) { if (flags & SGCN_DXF_ADD2_PLANE) SGCN_FJ_P(true, true, 2); else SGCN_FJ_P(true, true, 1); }
-      else if (add1) { if (add2) SGCN_FJ_P(true, true, 0); else SGCN_FJ_P(true, false, 0); }
-      else { if (add2) SGCN_FJ_P(false, true, 0); else SGCN_FJ_P(false, false, 0); }
-#undef SGCN_FJ_P
-#undef SGCN_FJ_T
-#undef SGCN_FJ_L
-#undef SGCN_FJ
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (add2_mask) {   // the identity-unit form: add1 given, add2 masked by add2_mask
-    if (pp)
-      gcn_dx_finish_kernel<true, true, true, true><<<B * C, kThreads, 0, st>>>(
-          dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
-          add2_mask, flags);
-    else
-      gcn_dx_finish_kernel<true, true, false, true><<<B * C, kThreads, 0, st>>>(
-          dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
-          add2_mask, flags);
-    SGCN_LAUNCH_CHECK();
-    return 0;
-  }
-#define SGCN_FIN(A1, A2, PT)                                                                \
-  gcn_dx_finish_kernel<A1, A2, PT><<<B * C, kThreads, 0, st>>>(                           \
-      dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,  \
-      nullptr, flags)
-#define SGCN_FIN_P(A1, A2)                                                                  \
-  do {                                                                                      \
-    if (pp) SGCN_FIN(A1, A2, true);                                                         \
-    else SGCN_FIN(A1, A2, false);                                                           \
-  } while (0)
-  if (add1) { if (add2) SGCN_FIN_P(true, true); else SGCN_FIN_P(true, false); }
-  else { if (add2) SGCN_FIN_P(false, true); else SGCN_FIN_P(false, false); }
-#undef SGCN_FIN_P
-#undef SGCN_FIN
+  // add2_mask: the identity-unit form (add1 given, add2 masked by add2_mask). (Plane-resident,
+  // it holds ~200 VGPRs at 256 x 32 — two workgroups per CU — but 512 x 16, twice the waves,
+  // measured 2 % slower: profiles/r05_ar/ab_dx_finish_512.txt)
+  const bool a1 = add1 != nullptr, a2 = add2 != nullptr, pt = pp != nullptr;
+  auto ja = [&](auto NT, auto LPT, auto A1, auto A2, auto PT, auto A2M) {
+    gcn_dx_finish_ja_kernel<NT, LPT, A1, A2, PT, A2M><<<B * C, int(NT), 0, st>>>(
+        dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
+        add2_mask, flags);
+  };
+  auto loop = [&](auto A1, auto A2, auto PT, auto A2M) {
+    gcn_dx_finish_kernel<A1, A2, PT, A2M != 0><<<B * C, kThreads, 0, st>>>(
+        dxt, x0, m, add1, add2, dx, dmask_part, prev_s, prev_mean, prev_invstd, pp, C, T, V,
+        add2_mask, flags);
+  };
+  // A2M: 0 no mask, 1 add2 masked per element, 2 add2 holds one value per plane
+  const bool ok = add2_mask ? launch_plane(T, V, ja, loop, Const<true>{}, Const<true>{}, pt,
+                                           OneOf<1, 2>{flags & SGCN_DXF_ADD2_PLANE ? 2 : 1})
+                            : launch_plane(T, V, ja, loop, a1, a2, pt, Const<0>{});
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }

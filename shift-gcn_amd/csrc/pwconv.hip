@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace sgcn {
 namespace {
@@ -1315,16 +1316,10 @@ void launch_pwg(const FwdArgs& a, bool accum, hipStream_t st) {
   const long long P = (long long)a.B * a.T * a.V;   // < 2^31 (checked by the caller)
   dim3 grid((unsigned)((P + BN - 1) / BN), (a.M + BM - 1) / BM);
   const bool mask = a.mask != nullptr, xrot = a.x.rsign != 0, amc = a.a_mcontig != 0;
-#define SGCN_PWG(MS, XR, AM, AC) \
-  pwg_fwd_kernel<BM, BN, WM, WN, MS, XR, AM, AC, false, AR><<<grid, 64 * WM * WN, 0, st>>>(a)
-#define SGCN_PWG_AC(MS, XR, AM) \
-  (accum ? SGCN_PWG(MS, XR, AM, true) : SGCN_PWG(MS, XR, AM, false))
-#define SGCN_PWG_AM(MS, XR) (amc ? SGCN_PWG_AC(MS, XR, true) : SGCN_PWG_AC(MS, XR, false))
-  if (mask) { if (xrot) SGCN_PWG_AM(true, true); else SGCN_PWG_AM(true, false); }
-  else { if (xrot) SGCN_PWG_AM(false, true); else SGCN_PWG_AM(false, false); }
-#undef SGCN_PWG_AM
-#undef SGCN_PWG_AC
-#undef SGCN_PWG
+  with_consts([&](auto MASK, auto XROT, auto AMC, auto ACCUM) {
+    pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, AMC, ACCUM, false, AR>
+        <<<grid, 64 * WM * WN, 0, st>>>(a);
+  }, mask, xrot, amc, accum);
 }
 
 template <int BM, int BN, int WM, int WN>
@@ -1376,18 +1371,9 @@ void launch_dw3_t(const DwArgs& a, int S, int tiles, hipStream_t st) {
   dim3 grid(tiles, S);
   const bool mask = a.mask != nullptr, gr = a.g.rsign != 0, xr = a.x.rsign != 0,
              bias = a.bslab != nullptr;
-#define SGCN_DW3(MS, GR, XR, BI) \
-  pw_dw3_kernel<BM, BN, WM, WN, BKP, MS, GR, XR, BI><<<grid, 64 * WM * WN, 0, st>>>(a)
-#define SGCN_DW3_BI(MS, GR, XR) (bias ? SGCN_DW3(MS, GR, XR, true) : SGCN_DW3(MS, GR, XR, false))
-  if (mask) {
-    if (gr) { if (xr) SGCN_DW3_BI(true, true, true); else SGCN_DW3_BI(true, true, false); }
-    else { if (xr) SGCN_DW3_BI(true, false, true); else SGCN_DW3_BI(true, false, false); }
-  } else {
-    if (gr) { if (xr) SGCN_DW3_BI(false, true, true); else SGCN_DW3_BI(false, true, false); }
-    else { if (xr) SGCN_DW3_BI(false, false, true); else SGCN_DW3_BI(false, false, false); }
-  }
-#undef SGCN_DW3_BI
-#undef SGCN_DW3
+  with_consts([&](auto MASK, auto GROT, auto XROT, auto BIAS) {
+    pw_dw3_kernel<BM, BN, WM, WN, BKP, MASK, GROT, XROT, BIAS><<<grid, 64 * WM * WN, 0, st>>>(a);
+  }, mask, gr, xr, bias);
 }
 
 // launches pw_dw3 for one dW into the slab workspace; returns the split count used
@@ -1648,13 +1634,10 @@ int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_t
     a.bslab = dbias ? (float*)ws + (size_t)S * M * Nc : nullptr;
     const int per = (int)((P + S - 1) / S);
     dim3 grid((M + 4 * kDwcRows - 1) / (4 * kDwcRows), S);
-#define SGCN_DWC_L(NC_) (mask ? pw_dw_smallc_kernel<NC_, true><<<grid, 256, 0, st>>>(a, per) \
-                              : pw_dw_smallc_kernel<NC_, false><<<grid, 256, 0, st>>>(a, per))
-    if (Nc == 1) SGCN_DWC_L(1);
-    else if (Nc == 2) SGCN_DWC_L(2);
-    else if (Nc == 3) SGCN_DWC_L(3);
-    else SGCN_DWC_L(4);
-#undef SGCN_DWC_L
+    const bool ok = with_consts([&](auto NC, auto MASK) {
+      pw_dw_smallc_kernel<NC, MASK><<<grid, 256, 0, st>>>(a, per);
+    }, OneOf<1, 2, 3, 4>{Nc}, mask != nullptr);
+    SGCN_REQUIRE(ok);
   } else if (use_dw3(M, Nc)) {
     a.g_bytes = plane_bytes(g_bstride, g_cstride, g_tstride, B, M, T, V);
     a.x_bytes = plane_bytes(x_bstride, x_cstride, x_tstride, B, Nc, T, V);
@@ -1685,22 +1668,19 @@ int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_t
       a.g_bytes = plane_bytes(g_bstride, g_cstride, g_tstride, B, M, T, V);
       a.x_bytes = plane_bytes(x_bstride, x_cstride, x_tstride, B, Nc, T, V);
     }
-#define SGCN_DW(BM_, BN_)                                                                    \
-    (mask ? pw_dw_kernel<BM_, BN_, BM_ / 32, 2, true>                                           \
-                <<<grid, 64 * (BM_ / 32) * 2, (size_t)V * BN_ * sizeof(float), st>>>(a)       \
-          : plain ? pw_dw_kernel<BM_, BN_, BM_ / 32, 2, false, true><<<grid, 64 * (BM_ / 32) * 2, 0, st>>>(a) \
-          : pw_dw_kernel<BM_, BN_, BM_ / 32, 2, false><<<grid, 64 * (BM_ / 32) * 2, 0, st>>>(a))
-    if (bm == 128 && bn == 128) SGCN_DW(128, 128);
-    else if (bm == 128) SGCN_DW(128, 64);
-    else if (bn == 128) SGCN_DW(64, 128);
+    auto tile = [&](auto BM, auto BN, auto MASK, auto PLAIN) {
+      constexpr int WM = BM / 32;
+      pw_dw_kernel<BM, BN, WM, 2, MASK, PLAIN>
+          <<<grid, 64 * WM * 2, MASK ? (size_t)V * BN * sizeof(float) : 0, st>>>(a);
+    };
+    const OneOf<64, 128> tm{bm}, tn{bn};
 #ifdef SGCN_DIAG_DW64_SKIP
     // timing bound only: the 64 x 64 weight gradients are not computed (the slabs keep
     // whatever they held), the most a dX + dW fusion at C = 64 could remove
-    else if (!plain) SGCN_DW(64, 64);
-#else
-    else SGCN_DW(64, 64);
+    if (bm == 64 && bn == 64 && plain) {} else
 #endif
-#undef SGCN_DW
+    if (mask) with_consts(tile, tm, tn, Const<true>{}, Const<false>{});
+    else with_consts(tile, tm, tn, Const<false>{}, plain);
   }
   SGCN_LAUNCH_CHECK();
   launch_slab_reduce(a.slab, a.bslab, S, M, Nc, dw, dw_transpose, dw_accumulate, dbias,

@@ -25,13 +25,13 @@
 // Arithmetic follows the reference expression order with contraction disabled, so
 // outputs are bit-identical to the oracle restatement (oracle/shift_oracle.py).
 #include "common.hpp"
+#include "dispatch.hpp"
+#include "launch_forms.hpp"
 
 #pragma clang fp contract(off)
 
 namespace sgcn {
 namespace {
-
-constexpr int kThreads = 256;
 
 // kReverse note: every shift kernel walks its planes last to first. Its main input was
 // written front to back just before it (the contraction output R, the gcn tail's H, the
@@ -322,17 +322,8 @@ __global__ __launch_bounds__(kThreads) void tshift_bwd_kernel(
 // Same expressions in the same order as the global-tap kernels above, so the results
 // are bit-identical to them (and to the oracle).
 // ------------------------------------------------------------------------------------
-constexpr int kFwdLdsMax = 8192;    // floats of the staged input plane (32 KiB), 256 threads
-constexpr int kFwdLdsMax2 = 16384;  // ... with 512 threads (e.g. MediaPipe T=300: 9,900)
-constexpr int kBwdLdsMax = 16384;   // floats of the staged gout + input planes (64 KiB)
-
-// Zero-padded LDS planes (the stride-1 backward and the forward kernels below): an H x W
-// plane is staged with row pitch WP = W + 2 (a zero column each side) between kPadRows
-// zero rows above and below, element (h, w) at [(h + kPadRows) * WP + w + 1]; a tap of a
-// shift with floor(x) in {-1, 0} and |floor(y)| < kPadRows then needs no range check.
-constexpr int kPadRows = 4;
-
-__host__ __device__ constexpr int ra_pad_floats(int H, int W) { return (H + 2 * kPadRows) * (W + 2); }
+// (plane limits kFwdLdsMax / kFwdLdsMax2 / kBwdLdsMax and the zero-padded LDS plane layout,
+// kPadRows / ra_pad_floats: launch_forms.hpp)
 
 // zero the padding of a padded H x W plane (NT threads)
 template <int NT>
@@ -1286,202 +1277,32 @@ __device__ __forceinline__ void pos_finalize_body(const float2* __restrict__ pgr
   }
 }
 
-template <int EPT>
-void launch_fwd(bool affine, bool stats, const float* in, float* out, const float* xpos,
-                const float* ypos, const float* scale, const float* shift, float2* ps, int B,
-                int C, int H, int W, int Ho, int stride, int add_half, hipStream_t st) {
-  dim3 grid(B * C), block(kThreads);
-#define SGCN_FWD(A, S)                                                                     \
-  tshift_fwd_kernel<EPT, A, S><<<grid, block, 0, st>>>(in, out, xpos, ypos, scale, shift, \
-                                                      ps, C, H, W, Ho, stride, add_half)
-  if (affine) {
-    if (stats) SGCN_FWD(true, true); else SGCN_FWD(true, false);
-  } else {
-    if (stats) SGCN_FWD(false, true); else SGCN_FWD(false, false);
-  }
-#undef SGCN_FWD
-}
+// tshift_bwd_ra_kernel's arguments (null / 0 where the form does not read them)
+struct RaArgs {
+  const float *gout, *in, *xpos, *ypos, *scale, *shift, *bmu, *bis;
+  float* gin;
+  float2 *pg, *bp;
+  int B, C, H, W;
+  const float *gdy, *gy, *gx, *gcoef;   // GP
+  int gdyp;
+  const float *gz, *gzm, *gzi;          // GBN
+  float* gzpart;
+  const float *gd, *gdm, *gdi;          // GBD
+  float* gdpart;
+};
 
-// LDS path: EPT = LPT (the output plane is never larger than the staged input plane)
-template <int LPT, int NT = kThreads>
-void launch_fwd_lds(bool affine, bool stats, const float* in, float* out, const float* xpos,
-                    const float* ypos, const float* scale, const float* shift, float2* ps,
-                    int B, int C, int H, int W, int Ho, int stride, int add_half,
-                    hipStream_t st) {
-  dim3 grid(B * C), block(NT);
-  const size_t lds = (size_t)H * W * sizeof(float);
-#define SGCN_FWDL(A, S)                                                                  \
-  tshift_fwd_lds_kernel<NT, LPT, LPT, A, S><<<grid, block, lds, st>>>(                    \
-      in, out, xpos, ypos, scale, shift, ps, C, H, W, Ho, stride, add_half)
-  if (affine) {
-    if (stats) SGCN_FWDL(true, true); else SGCN_FWDL(true, false);
-  } else {
-    if (stats) SGCN_FWDL(false, true); else SGCN_FWDL(false, false);
-  }
-#undef SGCN_FWDL
-}
-
-// elements per thread of the padded joint-aligned forward kernels (W <= 64) on NT threads;
-// 0 when the plane needs more than 32 per thread or more than 64 KiB of LDS
-int pad_fwd_lpt(int H, int W, int nt) {
-  if (W > 64) return 0;
-  const int ntj = (nt / W) * W, per = (H * W + ntj - 1) / ntj;
-  // 512 threads also at 12 / 20 (as ra_lpt): MediaPipe's 9,900-float planes are 20 per
-  // thread, and the eval pre / tail forms held 88-95 VGPRs at 24 (two workgroups per CU)
-  int lpt = per <= 8 ? 8 : (per <= 16 ? 16 : (per <= 24 ? 24 : (per <= 32 ? 32 : 0)));
-  if (nt == 512 && per > 8 && per <= 12) lpt = 12;
-  if (nt == 512 && per > 16 && per <= 20) lpt = 20;
-  return (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float) > 65536 ? 0 : lpt;
-}
-
-// padded joint-aligned forward (W <= 64): LPT elements per thread on the (NT / W) * W
-// stride; false (nothing launched) when the plane needs more than 32 per thread or
-// more than 64 KiB of LDS
-template <int NT>
-bool launch_fwd_pad(bool affine, bool stats, const float* in, float* out, const float* xpos,
-                    const float* ypos, const float* scale, const float* shift, float2* ps,
-                    int B, int C, int H, int W, int Ho, int stride, int add_half,
-                    hipStream_t st) {
-  const int lpt = pad_fwd_lpt(H, W, NT);
-  const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-  if (lpt == 0) return false;
-#define SGCN_FWDP(L, A, S)                                                                   \
-  tshift_fwd_pad_kernel<NT, L, 0, A, S><<<B * C, NT, lds, st>>>(                             \
-      in, out, xpos, ypos, scale, shift, ps, C, H, W, Ho, stride, add_half, nullptr, nullptr, \
-      nullptr, nullptr, nullptr, nullptr, nullptr)
-#define SGCN_FWDP_AS(L)                                                                      \
-  do {                                                                                       \
-    if (affine) { if (stats) SGCN_FWDP(L, true, true); else SGCN_FWDP(L, true, false); }     \
-    else { if (stats) SGCN_FWDP(L, false, true); else SGCN_FWDP(L, false, false); }          \
-  } while (0)
-  if (lpt == 8) SGCN_FWDP_AS(8); else if (lpt == 12) SGCN_FWDP_AS(12); else if (lpt == 16) SGCN_FWDP_AS(16);
-  else if (lpt == 20) SGCN_FWDP_AS(20); else if (lpt == 24) SGCN_FWDP_AS(24); else SGCN_FWDP_AS(32);
-#undef SGCN_FWDP_AS
-#undef SGCN_FWDP
-  return true;
-}
-
-template <int EPT, int STRIDE>
-void launch_bwd(bool affine, bool relu, const float* gout, const float* in, const float* xpos,
-                const float* ypos, const float* scale, const float* shift, const float* bmu,
-                const float* bis, float* gin, float2* pg, float2* bp, int B, int C, int H,
-                int W, int Ho, int add_half, hipStream_t st) {
-  dim3 grid(B * C), block(kThreads);
-#define SGCN_BWD(A, R, P)                                                                    \
-  tshift_bwd_kernel<EPT, A, R, STRIDE, P><<<grid, block, 0, st>>>(                            \
-      gout, in, xpos, ypos, scale, shift, bmu, bis, gin, pg, bp, C, H, W, Ho, add_half)
-  if (bp) {
-    if (affine) {
-      if (relu) SGCN_BWD(true, true, true); else SGCN_BWD(true, false, true);
-    } else {
-      if (relu) SGCN_BWD(false, true, true); else SGCN_BWD(false, false, true);
-    }
-  } else {
-    if (affine) {
-      if (relu) SGCN_BWD(true, true, false); else SGCN_BWD(true, false, false);
-    } else {
-      if (relu) SGCN_BWD(false, true, false); else SGCN_BWD(false, false, false);
-    }
-  }
-#undef SGCN_BWD
-}
-
-constexpr int kBwdThreads = 512;
-
-template <int LPT, bool JA>
-void launch_bwd_s2(bool affine, bool relu, const float* gout, const float* in,
-                   const float* xpos, const float* ypos, const float* scale,
-                   const float* shift, const float* bmu, const float* bis, float* gin,
-                   float2* pg, float2* bp, int B, int C, int H, int W, int Ho, int add_half,
-                   hipStream_t st) {
-  constexpr int NT = kBwdThreads;
-  dim3 grid(B * C), block(NT);
-  const size_t lds = (size_t)(H + Ho) * W * sizeof(float);
-#define SGCN_BWDL(A, R, P)                                                                  \
-  tshift_bwd_s2_kernel<NT, LPT, A, R, P, JA><<<grid, block, lds, st>>>(                      \
-      gout, in, xpos, ypos, scale, shift, bmu, bis, gin, pg, bp, C, H, W, Ho, add_half)
-  if (bp) {
-    if (affine) {
-      if (relu) SGCN_BWDL(true, true, true); else SGCN_BWDL(true, false, true);
-    } else {
-      if (relu) SGCN_BWDL(false, true, true); else SGCN_BWDL(false, false, true);
-    }
-  } else {
-    if (affine) {
-      if (relu) SGCN_BWDL(true, true, false); else SGCN_BWDL(true, false, false);
-    } else {
-      if (relu) SGCN_BWDL(false, true, false); else SGCN_BWDL(false, false, false);
-    }
-  }
-#undef SGCN_BWDL
-}
-
-int pick_lpt(int n, int nt) {
-  const int per = (n + nt - 1) / nt;
-  return per <= 8 ? 8 : (per <= 16 ? 16 : 32);
-}
-
-// elements per thread of the joint-aligned stride-1 LDS backward kernels (stride
-// (nt / W) * W); 0 = the plane does not fit 32 per thread. 512-thread workgroups also take
-// 12 and 20: a thread holds ~5 VGPRs per element, and at 24 the shift_out backward (bnin)
-// and the GBD backward held 141-143 VGPRs — one 512-thread workgroup per CU on MediaPipe's
-// 9,900-float planes (W = 33, exactly 20 per thread); at 20 two fit (likewise 12 against 16
-// for its 4,950-float T = 150 planes: three instead of two)
-int ra_lpt(int n, int nt, int W) {
-  const int nte = (nt / W) * W;
-  if (nte <= 0 || W > 64) return 0;
-  const int per = (n + nte - 1) / nte;
-  if (nt == 512 && per > 8 && per <= 12) return 12;
-  if (nt == 512 && per > 16 && per <= 20) return 20;
-  return per <= 8 ? 8 : (per <= 16 ? 16 : (per <= 24 ? 24 : (per <= 32 ? 32 : 0)));
-}
-
-// largest stride-1 plane the joint-aligned backward kernels with affine taps (shift_in:
-// plain and GBN) run on 256-thread workgroups (up to 32 elements per thread): at NTU T=300
-// (7,500 floats) measured 8 % (GBN) / 4 % (plain) faster than 512 threads; the shift_out
-// backward (bnin) keeps 512 threads above 4,096 floats (no difference)
-constexpr int kRaSplit256 = 8192;
-#ifndef SGCN_GBD_SPLIT
-#define SGCN_GBD_SPLIT 1
-#endif
-
-// LDS bytes of the padded stride-1 backward (GBN reuses it for 6*NT partial sums)
-size_t ra_lds_bytes(int H, int W, int nt, bool gbn) {
-  const int f = ra_pad_floats(H, W);
-  return (size_t)(gbn ? max(f + 1, 6 * nt) : f + 1) * sizeof(float);   // + the spare float
-}
-constexpr size_t kRaLdsMax = 65536;
-
-// launch tshift_bwd_ra_kernel on nt threads (256 or 512) with LPT = ra_lpt(H*W, nt, W);
-// returns false (nothing launched) when the plane does not fit its LDS or registers
-template <bool AFFINE, bool RELU, bool BNP, int GP, bool GBN, bool GBD = false>
-bool launch_ra(int nt, const float* gout, const float* in, const float* xpos,
-               const float* ypos, const float* scale, const float* shift, const float* bmu,
-               const float* bis, float* gin, float2* pg, float2* bp, int B, int C, int H,
-               int W, const float* gdy, const float* gy, const float* gx, const float* gcoef,
-               const float* gz, const float* gzm, const float* gzi, float* gzpart,
-               hipStream_t st, const float* gd = nullptr, const float* gdm = nullptr,
-               const float* gdi = nullptr, float* gdpart = nullptr, int gdyp = 0) {
-  const int lpt = ra_lpt(H * W, nt, W);
-  const size_t lds = ra_lds_bytes(H, W, nt, GBN);
-  if (lpt == 0 || lds > kRaLdsMax) return false;
-#define SGCN_RA(NT, L)                                                                         \
-  tshift_bwd_ra_kernel<NT, L, AFFINE, RELU, BNP, GP, GBN, GBD><<<B * C, NT, lds, st>>>(        \
-      gout, in, xpos, ypos, scale, shift, bmu, bis, gin, pg, bp, C, H, W, gdy, gy, gx, gcoef,  \
-      gz, gzm, gzi, gzpart, gd, gdm, gdi, gdpart, gdyp)
-  if (nt == 256) {
-    if (lpt == 8) SGCN_RA(256, 8); else if (lpt == 16) SGCN_RA(256, 16); else if (lpt == 24) SGCN_RA(256, 24); else SGCN_RA(256, 32);
-  } else {
-    if (lpt == 8) SGCN_RA(512, 8); else if (lpt == 12) SGCN_RA(512, 12); else if (lpt == 16) SGCN_RA(512, 16);
-    else if (lpt == 20) SGCN_RA(512, 20); else if (lpt == 24) SGCN_RA(512, 24); else SGCN_RA(512, 32);
-  }
-#undef SGCN_RA
-  return true;
-}
-
-int pick_ept(int n) {
-  const int per = (n + kThreads - 1) / kThreads;
-  return per <= 8 ? 8 : (per <= 16 ? 16 : 32);
+// launch tshift_bwd_ra_kernel on f's (threads, elements per thread), one of Forms, with the
+// flags AFFINE, RELU, BNP, GP, GBN, GBD (dispatch.hpp); false: nothing launched
+template <const auto& Forms, class... A>
+bool launch_ra(const LaunchForm& f, const RaArgs& a, hipStream_t st, A... flags) {
+  return with_form<Forms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto RELU, auto BNP,
+                                           auto GP, auto GBN, auto GBD) {
+    tshift_bwd_ra_kernel<NT, LPT, AFFINE, RELU, BNP, GP, GBN, GBD>
+        <<<a.B * a.C, int(NT), ra_lds_bytes(a.H, a.W, NT, GBN), st>>>(
+            a.gout, a.in, a.xpos, a.ypos, a.scale, a.shift, a.bmu, a.bis, a.gin, a.pg, a.bp, a.C,
+            a.H, a.W, a.gdy, a.gy, a.gx, a.gcoef, a.gz, a.gzm, a.gzi, a.gzpart, a.gd, a.gdm,
+            a.gdi, a.gdpart, a.gdyp);
+  }, flags...);
 }
 
 }  // namespace
@@ -1504,33 +1325,28 @@ int sgcn_tshift_fwd(const float* in, float* out, const float* xpos, const float*
   const bool aff = in_scale != nullptr, stats = plane_stats != nullptr;
   float2* ps = (float2*)plane_stats;
   const int ah = (ypos_is_raw && stride != 1) ? 1 : 0;
-  // padded joint-aligned kernel (W <= 64): 256 threads up to kFwdLdsMax floats, else 512
-  if (H * W <= kFwdLdsMax2 &&
-      (H * W <= kFwdLdsMax
-           ? launch_fwd_pad<kThreads>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st)
-           : launch_fwd_pad<512>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st))) {
-    SGCN_LAUNCH_CHECK();
-    return 0;
+  const LaunchForm f = tshift_fwd_form(H, W, stride);
+  bool ok;
+  if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
+    const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
+    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
+      tshift_fwd_pad_kernel<NT, LPT, 0, AFFINE, STATS><<<B * C, int(NT), lds, st>>>(
+          in, out, xpos, ypos, in_scale, in_shift, ps, C, H, W, Ho, stride, ah);
+    }, aff, stats);
+  } else if (f.kind == Kind::lds) {
+    // EPT = LPT (the output plane is never larger than the staged input plane)
+    const size_t lds = (size_t)H * W * sizeof(float);
+    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
+      tshift_fwd_lds_kernel<NT, LPT, LPT, AFFINE, STATS><<<B * C, int(NT), lds, st>>>(
+          in, out, xpos, ypos, in_scale, in_shift, ps, C, H, W, Ho, stride, ah);
+    }, aff, stats);
+  } else {
+    ok = with_consts([&](auto EPT, auto AFFINE, auto STATS) {
+      tshift_fwd_kernel<EPT, AFFINE, STATS><<<B * C, kThreads, 0, st>>>(
+          in, out, xpos, ypos, in_scale, in_shift, ps, C, H, W, Ho, stride, ah);
+    }, OneOf<8, 16, 32>{f.lpt}, aff, stats);
   }
-  if (H * W <= kFwdLdsMax) {
-    switch (pick_lpt(H * W, kThreads)) {
-      case 8: launch_fwd_lds<8>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-      case 16: launch_fwd_lds<16>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-      default: launch_fwd_lds<32>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-    }
-    SGCN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (H * W <= kFwdLdsMax2) {   // 512 threads x 32 staged elements
-    launch_fwd_lds<32, 512>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st);
-    SGCN_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (pick_ept(Ho * W)) {
-    case 8: launch_fwd<8>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-    case 16: launch_fwd<16>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-    default: launch_fwd<32>(aff, stats, in, out, xpos, ypos, in_scale, in_shift, ps, B, C, H, W, Ho, stride, ah, st); break;
-  }
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1540,9 +1356,10 @@ int sgcn_tshift_fwd_pre(const float* z, float* out, const float* xpos, const flo
                         const float* r_scale, const float* r_shift, const float* in_scale,
                         const float* in_shift, int B, int C, int H, int W, int stride,
                         int ypos_is_raw, void* stream) {
-  SGCN_REQUIRE(B >= 0 && C > 0 && H >= 0 && W > 0 && W <= 1024 && stride >= 1);
+  SGCN_REQUIRE(B >= 0 && C > 0 && H >= 0 && W > 0 && stride >= 1);
   SGCN_REQUIRE((r_scale == nullptr) == (r_shift == nullptr));
-  SGCN_REQUIRE(H * W <= kFwdLdsMax2);   // LDS-staged planes only (caller falls back)
+  const LaunchForm f = fwd_fused_form(H, W);
+  SGCN_REQUIRE(f.kind != Kind::refuse);   // LDS-staged planes only (caller falls back)
   const int Ho = H / stride;
   if (B == 0 || Ho == 0) return 0;
   SGCN_REQUIRE(z && out && xpos && ypos && pre_scale && pre_shift && r && in_scale &&
@@ -1550,48 +1367,24 @@ int sgcn_tshift_fwd_pre(const float* z, float* out, const float* xpos, const flo
   SGCN_REQUIRE((long long)B * C < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
   const int ah = (ypos_is_raw && stride != 1) ? 1 : 0;
-  {   // padded joint-aligned kernel (W <= 64)
-    const int nt = H * W <= kFwdLdsMax ? kThreads : 512;
-    const int lpt = pad_fwd_lpt(H, W, nt);
-    if (lpt) {
-      const size_t plds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-#define SGCN_PREP(NT, L, R)                                                                    \
-  tshift_fwd_pad_kernel<NT, L, 1, true, false, R><<<B * C, NT, plds, st>>>(                    \
-      z, out, xpos, ypos, in_scale, in_shift, nullptr, C, H, W, Ho, stride, ah, pre_scale,      \
-      pre_shift, r, r_scale, r_shift)
-#define SGCN_PREP_R(NT, L) \
-  do { if (r_scale) SGCN_PREP(NT, L, 2); else SGCN_PREP(NT, L, 1); } while (0)
-      if (nt == kThreads) {
-        if (lpt == 8) SGCN_PREP_R(kThreads, 8); else if (lpt == 16) SGCN_PREP_R(kThreads, 16); else if (lpt == 24) SGCN_PREP_R(kThreads, 24); else SGCN_PREP_R(kThreads, 32);
-      } else {
-        if (lpt == 8) SGCN_PREP_R(512, 8); else if (lpt == 12) SGCN_PREP_R(512, 12); else if (lpt == 16) SGCN_PREP_R(512, 16);
-        else if (lpt == 20) SGCN_PREP_R(512, 20); else if (lpt == 24) SGCN_PREP_R(512, 24); else SGCN_PREP_R(512, 32);
-      }
-#undef SGCN_PREP_R
-#undef SGCN_PREP
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  const size_t lds = (size_t)H * W * sizeof(float);
-#define SGCN_PRE(NT, L, R)                                                                     \
-  tshift_fwd_pre_kernel<NT, L, R><<<B * C, NT, lds, st>>>(z, out, xpos, ypos, pre_scale,       \
-                                                           pre_shift, r, r_scale, r_shift,     \
-                                                           in_scale, in_shift, C, H, W, Ho,    \
-                                                           stride, ah)
-#define SGCN_PRE_R(NT, L) \
-  do { if (r_scale) SGCN_PRE(NT, L, 2); else SGCN_PRE(NT, L, 1); } while (0)
-  if (H * W <= kFwdLdsMax) {
-    switch (pick_lpt(H * W, kThreads)) {
-      case 8: SGCN_PRE_R(kThreads, 8); break;
-      case 16: SGCN_PRE_R(kThreads, 16); break;
-      default: SGCN_PRE_R(kThreads, 32); break;
-    }
+  const OneOf<1, 2> res{r_scale ? 2 : 1};
+  bool ok;
+  if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
+    const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
+    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES) {
+      tshift_fwd_pad_kernel<NT, LPT, 1, true, false, RES><<<B * C, int(NT), lds, st>>>(
+          z, out, xpos, ypos, in_scale, in_shift, nullptr, C, H, W, Ho, stride, ah, pre_scale,
+          pre_shift, r, r_scale, r_shift);
+    }, res);
   } else {
-    SGCN_PRE_R(512, 32);
+    const size_t lds = (size_t)H * W * sizeof(float);
+    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES) {
+      tshift_fwd_pre_kernel<NT, LPT, RES><<<B * C, int(NT), lds, st>>>(
+          z, out, xpos, ypos, pre_scale, pre_shift, r, r_scale, r_shift, in_scale, in_shift, C,
+          H, W, Ho, stride, ah);
+    }, res);
   }
-#undef SGCN_PRE_R
-#undef SGCN_PRE
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1601,67 +1394,36 @@ int sgcn_tshift_fwd_tail(const float* in, float* out, const float* xpos, const f
                          const float* r_scale, const float* r_shift, const float* gather_m,
                          float* out_gathered, int B, int C, int H, int W, int stride,
                          int ypos_is_raw, void* stream) {
-  SGCN_REQUIRE(B >= 0 && C > 0 && H >= 0 && W > 0 && W <= 1024 && stride >= 1);
+  SGCN_REQUIRE(B >= 0 && C > 0 && H >= 0 && W > 0 && stride >= 1);
   SGCN_REQUIRE((r_scale == nullptr) == (r_shift == nullptr) && (r || !r_scale));
   SGCN_REQUIRE((gather_m == nullptr) == (out_gathered == nullptr));
-  SGCN_REQUIRE(H * W <= kFwdLdsMax2);   // LDS-staged planes only (caller falls back)
+  const LaunchForm f = fwd_fused_form(H, W);
+  SGCN_REQUIRE(f.kind != Kind::refuse);   // LDS-staged planes only (caller falls back)
   const int Ho = H / stride;
   if (B == 0 || Ho == 0) return 0;
   SGCN_REQUIRE(in && out && xpos && ypos && post_scale && post_shift && out != in);
   SGCN_REQUIRE((long long)B * C < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
   const int ah = (ypos_is_raw && stride != 1) ? 1 : 0;
-  const int res = r == nullptr ? 0 : (r_scale ? 2 : 1);
+  const OneOf<0, 1, 2> res{r == nullptr ? 0 : (r_scale ? 2 : 1)};
   const bool go = out_gathered != nullptr;
-  {   // padded joint-aligned kernel (W <= 64)
-    const int nt = H * W <= kFwdLdsMax ? kThreads : 512;
-    const int lpt = pad_fwd_lpt(H, W, nt);
-    if (lpt) {
-      const size_t plds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-#define SGCN_TAILP(NT, L, R, G)                                                                \
-  tshift_fwd_pad_kernel<NT, L, 2, false, false, R, G><<<B * C, NT, plds, st>>>(                \
-      in, out, xpos, ypos, post_scale, post_shift, nullptr, C, H, W, Ho, stride, ah, nullptr,  \
-      nullptr, r, r_scale, r_shift, gather_m, out_gathered)
-#define SGCN_TAILP_RG(NT, L)                                                                   \
-  do {                                                                                         \
-    if (res == 0) { if (go) SGCN_TAILP(NT, L, 0, true); else SGCN_TAILP(NT, L, 0, false); }    \
-    else if (res == 1) { if (go) SGCN_TAILP(NT, L, 1, true); else SGCN_TAILP(NT, L, 1, false); } \
-    else { if (go) SGCN_TAILP(NT, L, 2, true); else SGCN_TAILP(NT, L, 2, false); }             \
-  } while (0)
-      if (nt == kThreads) {
-        if (lpt == 8) SGCN_TAILP_RG(kThreads, 8); else if (lpt == 16) SGCN_TAILP_RG(kThreads, 16); else if (lpt == 24) SGCN_TAILP_RG(kThreads, 24); else SGCN_TAILP_RG(kThreads, 32);
-      } else {
-        if (lpt == 8) SGCN_TAILP_RG(512, 8); else if (lpt == 12) SGCN_TAILP_RG(512, 12); else if (lpt == 16) SGCN_TAILP_RG(512, 16);
-        else if (lpt == 20) SGCN_TAILP_RG(512, 20); else if (lpt == 24) SGCN_TAILP_RG(512, 24); else SGCN_TAILP_RG(512, 32);
-      }
-#undef SGCN_TAILP_RG
-#undef SGCN_TAILP
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  const size_t lds = (size_t)H * W * sizeof(float);
-#define SGCN_TAIL(NT, L, R, G)                                                                \
-  tshift_fwd_tail_kernel<NT, L, R, G><<<B * C, NT, lds, st>>>(                                \
-      in, out, xpos, ypos, post_scale, post_shift, r, r_scale, r_shift, gather_m,            \
-      out_gathered, C, H, W, Ho, stride, ah)
-#define SGCN_TAIL_RG(NT, L)                                                                   \
-  do {                                                                                        \
-    if (res == 0) { if (go) SGCN_TAIL(NT, L, 0, true); else SGCN_TAIL(NT, L, 0, false); }     \
-    else if (res == 1) { if (go) SGCN_TAIL(NT, L, 1, true); else SGCN_TAIL(NT, L, 1, false); } \
-    else { if (go) SGCN_TAIL(NT, L, 2, true); else SGCN_TAIL(NT, L, 2, false); }              \
-  } while (0)
-  if (H * W <= kFwdLdsMax) {
-    switch (pick_lpt(H * W, kThreads)) {
-      case 8: SGCN_TAIL_RG(kThreads, 8); break;
-      case 16: SGCN_TAIL_RG(kThreads, 16); break;
-      default: SGCN_TAIL_RG(kThreads, 32); break;
-    }
+  bool ok;
+  if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
+    const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
+    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES, auto GOUT) {
+      tshift_fwd_pad_kernel<NT, LPT, 2, false, false, RES, GOUT><<<B * C, int(NT), lds, st>>>(
+          in, out, xpos, ypos, post_scale, post_shift, nullptr, C, H, W, Ho, stride, ah, nullptr,
+          nullptr, r, r_scale, r_shift, gather_m, out_gathered);
+    }, res, go);
   } else {
-    SGCN_TAIL_RG(512, 32);
+    const size_t lds = (size_t)H * W * sizeof(float);
+    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES, auto GOUT) {
+      tshift_fwd_tail_kernel<NT, LPT, RES, GOUT><<<B * C, int(NT), lds, st>>>(
+          in, out, xpos, ypos, post_scale, post_shift, r, r_scale, r_shift, gather_m,
+          out_gathered, C, H, W, Ho, stride, ah);
+    }, res, go);
   }
-#undef SGCN_TAIL_RG
-#undef SGCN_TAIL
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1671,7 +1433,9 @@ int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const 
                          float* gx, float* gy, void* ws, size_t ws_bytes, int B, int C, int H,
                          int W, int ypos_is_raw, int dy_plane, void* stream) {
   SGCN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0);
-  SGCN_REQUIRE(H * W <= kBwdLdsMax);   // LDS-staged stride-1 planes only (caller falls back)
+  // LDS-staged stride-1 planes only (caller falls back: ops.ra_fits)
+  const LaunchForm f = bnin_form(H, W);
+  SGCN_REQUIRE(f.kind == Kind::ra);
   SGCN_REQUIRE(dy && s && coef && in && xpos && ypos && gin && ws);
   SGCN_REQUIRE((gx == nullptr) == (gy == nullptr));
   SGCN_REQUIRE(ws_bytes >= sgcn_tshift_bwd_ws_bytes(B, C));
@@ -1679,21 +1443,16 @@ int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const 
   (void)ypos_is_raw;   // stride 1: the +0.5 of shift.py:17-18 never applies
   hipStream_t st = (hipStream_t)stream;
   float2* pg = (float2*)ws;
-  // 512 threads above 4K-float planes: 256 threads at NTU T = 300 measured 0.3 % slower per
-  // step (profiles/r03_x1b/ab_x1b_bound.txt, variant bnin256)
-  const int ntb = H * W <= 4096 ? 256 : 512;
-  const int dyp = dy_plane != 0;
+  RaArgs a{nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr, B, C, H, W};
+  a.gdy = dy;
+  a.gy = y;
+  a.gx = s;
+  a.gcoef = coef;
+  a.gdyp = dy_plane != 0;
   // y == NULL: dy already carries the ReLU mask (GP = 2: the y plane is not loaded)
-  const bool ok =
-      y ? launch_ra<false, true, false, 1, false>(
-              ntb, nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr,
-              B, C, H, W, dy, y, s, coef, nullptr, nullptr, nullptr, nullptr, st, nullptr,
-              nullptr, nullptr, nullptr, dyp)
-        : launch_ra<false, true, false, 2, false>(
-              ntb, nullptr, in, xpos, ypos, nullptr, nullptr, nullptr, nullptr, gin, pg, nullptr,
-              B, C, H, W, dy, nullptr, s, coef, nullptr, nullptr, nullptr, nullptr, st, nullptr,
-              nullptr, nullptr, nullptr, dyp);
-  SGCN_REQUIRE(ok);   // W <= 64, <= 32 elements per thread, padded plane <= 64 KiB (ops.ra_fits)
+  const bool ok = launch_ra<kBninForms>(f, a, st, Const<false>{}, Const<true>{}, Const<false>{},
+                                        OneOf<1, 2>{y ? 1 : 2}, Const<false>{}, Const<false>{});
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
   SGCN_LAUNCH_CHECK();
@@ -1739,9 +1498,12 @@ int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
                         float* z_part, const float* d, const float* d_mean,
                         const float* d_invstd, float* d_part, float* gin, float* gx, float* gy,
                         void* ws, size_t ws_bytes, int B, int C, int H, int W, void* stream) {
-  SGCN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && W <= 64);
+  SGCN_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0);
   SGCN_REQUIRE((d == nullptr) == (d_part == nullptr) && (!d || (d_mean && d_invstd)));
-  SGCN_REQUIRE(H * W <= kBwdLdsMax);   // LDS-staged stride-1 planes only (caller falls back)
+  // LDS-staged stride-1 planes only, within the largest LPT and 64 KiB of LDS (caller falls
+  // back: ops.ra_fits)
+  const LaunchForm f = gbn_form(H, W, d != nullptr);
+  SGCN_REQUIRE(f.kind == Kind::ra);
   SGCN_REQUIRE(gout && in && xpos && ypos && in_scale && in_shift && bn_mean && bn_invstd &&
                bn_part && z && z_mean && z_invstd && z_part && gin && ws);
   SGCN_REQUIRE((gx == nullptr) == (gy == nullptr));
@@ -1749,24 +1511,23 @@ int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
   SGCN_REQUIRE((long long)B * C < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
   float2* pg = (float2*)ws;
-  float2* bp = (float2*)bn_part;
-  // sgcn_tshift_bwd's stride-1 thread counts; elements per thread from the W-aligned
-  // stride (NT / W) * W; 512 threads when 256 would need more than 32 per thread. With the
-  // down BatchNorm's sums (GBD) a 32-element thread holds 183 VGPRs (two 256-thread
-  // workgroups per CU): such planes take 512 threads x 16 (107 VGPRs, two 512-thread
-  // workgroups) (SGCN_GBD_SPLIT=0: 256 threads as GBN)
-  const int n = H * W;
-  const int l256 = n <= kRaSplit256 ? ra_lpt(n, 256, W) : 0;
-  const int ntg = l256 && !(SGCN_GBD_SPLIT && d && l256 > 24) ? 256 : kBwdThreads;
-  const bool ok =
-      d ? launch_ra<true, false, true, false, true, true>(
-              ntg, gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, B,
-              C, H, W, nullptr, nullptr, nullptr, nullptr, z, z_mean, z_invstd, z_part, st, d,
-              d_mean, d_invstd, d_part)
-        : launch_ra<true, false, true, false, true>(
-              ntg, gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, B,
-              C, H, W, nullptr, nullptr, nullptr, nullptr, z, z_mean, z_invstd, z_part, st);
-  SGCN_REQUIRE(ok);   // within the largest LPT and 64 KiB of LDS (ops.ra_fits)
+  RaArgs a{gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg,
+           (float2*)bn_part, B, C, H, W};
+  a.gz = z;
+  a.gzm = z_mean;
+  a.gzi = z_invstd;
+  a.gzpart = z_part;
+  if (d) {
+    a.gd = d;
+    a.gdm = d_mean;
+    a.gdi = d_invstd;
+    a.gdpart = d_part;
+  }
+  const Const<true> on{};
+  const Const<false> off{};
+  const bool ok = d ? launch_ra<kGbdForms>(f, a, st, on, off, on, Const<0>{}, on, on)
+                    : launch_ra<kRaForms>(f, a, st, on, off, on, Const<0>{}, on, off);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
   SGCN_LAUNCH_CHECK();
@@ -1787,56 +1548,31 @@ int sgcn_tshift_bwd(const float* gout, const float* in, const float* xpos, const
   SGCN_REQUIRE(ws_bytes >= sgcn_tshift_bwd_ws_bytes(B, C));
   SGCN_REQUIRE((long long)H * W < (1LL << 30) && (long long)B * C < (1LL << 31));
   hipStream_t st = (hipStream_t)stream;
-  const bool aff = in_scale != nullptr, relu = relu_mask != 0;
+  const bool aff = in_scale != nullptr, relu = relu_mask != 0, bnp = bn_part != nullptr;
   float2* pg = (float2*)ws;
   float2* bp = (float2*)bn_part;
   const int ah = (ypos_is_raw && stride != 1) ? 1 : 0;
-  // stride 1: the padded joint-aligned LDS kernel (W <= 64, <= 32 elements per thread,
-  // <= 64 KiB of LDS); small planes (T = 150 / 75) on 256 threads, so fewer lanes idle per
-  // workgroup; anything else takes the global-tap kernel below
-  if (stride == 1 && H > 0) {
-    // (256 threads only where 32 elements per thread cover the plane, as the GBN launcher)
-    const int nt1 = H * W <= kRaSplit256 && ra_lpt(H * W, 256, W) ? 256 : kBwdThreads;
-    bool done;
-#define SGCN_RA1(A, R, P)                                                                       done = launch_ra<A, R, P, false, false>(nt1, gout, in, xpos, ypos, in_scale, in_shift,                                                 bn_mean, bn_invstd, gin, pg, bp, B, C, H, W, nullptr,                                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,                                           nullptr, st)
-    if (bp) {
-      if (aff) { if (relu) SGCN_RA1(true, true, true); else SGCN_RA1(true, false, true); }
-      else { if (relu) SGCN_RA1(false, true, true); else SGCN_RA1(false, false, true); }
-    } else {
-      if (aff) { if (relu) SGCN_RA1(true, true, false); else SGCN_RA1(true, false, false); }
-      else { if (relu) SGCN_RA1(false, true, false); else SGCN_RA1(false, false, false); }
-    }
-#undef SGCN_RA1
-    if (done) {
-      SGCN_LAUNCH_CHECK();
-      if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
-      SGCN_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  if (stride == 2 && (H + Ho) * W <= kBwdLdsMax && H > 0) {
-    const int lpt = pick_lpt((H + Ho) * W, kBwdThreads);
-#define SGCN_BWDL_LPT(L, J)                                                                   \
-  launch_bwd_s2<L, J>(aff, relu, gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, \
-                      gin, pg, bp, B, C, H, W, Ho, ah, st)
-    if (W <= 64) {   // joint-aligned walk (W <= NT)
-      if (lpt == 8) SGCN_BWDL_LPT(8, true); else if (lpt == 16) SGCN_BWDL_LPT(16, true);
-      else SGCN_BWDL_LPT(32, true);
-    } else {
-      if (lpt == 8) SGCN_BWDL_LPT(8, false); else if (lpt == 16) SGCN_BWDL_LPT(16, false);
-      else SGCN_BWDL_LPT(32, false);
-    }
-#undef SGCN_BWDL_LPT
+  const LaunchForm f = bwd_form(H, W, stride);
+  bool ok;
+  if (f.kind == Kind::ra) {
+    const RaArgs a{gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, B,
+                   C, H, W};
+    ok = launch_ra<kRaForms>(f, a, st, aff, relu, bnp, Const<0>{}, Const<false>{}, Const<false>{});
+  } else if (f.kind == Kind::s2) {   // f.flag: joint-aligned walk (W <= 64)
+    const size_t lds = (size_t)(H + Ho) * W * sizeof(float);
+    ok = with_consts([&](auto LPT, auto JA, auto AFFINE, auto RELU, auto BNP) {
+      tshift_bwd_s2_kernel<kBwdThreads, LPT, AFFINE, RELU, BNP, JA><<<B * C, kBwdThreads, lds, st>>>(
+          gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, C, H, W, Ho,
+          ah);
+    }, OneOf<8, 16, 32>{f.lpt}, f.flag, aff, relu, bnp);
   } else {
-  const int ept = pick_ept(H * W);
-#define SGCN_BWD_EPT(E)                                                                     \
-  (stride == 1 ? launch_bwd<E, 1>(aff, relu, gout, in, xpos, ypos, in_scale, in_shift, \
-                                  bn_mean, bn_invstd, gin, pg, bp, B, C, H, W, Ho, ah, st)                                   \
-               : launch_bwd<E, 2>(aff, relu, gout, in, xpos, ypos, in_scale, in_shift, \
-                                  bn_mean, bn_invstd, gin, pg, bp, B, C, H, W, Ho, ah, st))
-  if (ept == 8) SGCN_BWD_EPT(8); else if (ept == 16) SGCN_BWD_EPT(16); else SGCN_BWD_EPT(32);
-#undef SGCN_BWD_EPT
+    ok = with_consts([&](auto EPT, auto STRIDE, auto AFFINE, auto RELU, auto BNP) {
+      tshift_bwd_kernel<EPT, AFFINE, RELU, STRIDE, BNP><<<B * C, kThreads, 0, st>>>(
+          gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, C, H, W, Ho,
+          ah);
+    }, OneOf<8, 16, 32>{f.lpt}, OneOf<1, 2>{stride}, aff, relu, bnp);
   }
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
   SGCN_LAUNCH_CHECK();
