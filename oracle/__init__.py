@@ -16,7 +16,8 @@ import this package, and only as the checker / reported CPU baseline. The produc
 * :mod:`oracle.pw_ref`       — float64 torch restatements of the pointwise contractions
   (``sgcn_pw_fwd`` / ``sgcn_pw_dw`` / ``sgcn_pw_fwd_tshift``) through the header's plane
   addressing formula.
-* :mod:`oracle.pw_cases`     — their test's shape tables and host-chooser mirrors.
+* :mod:`oracle.pw_cases`     — their test's shape tables and mirrors of the host choosers
+  (``shift-gcn_amd/csrc/pw_forms.hpp``; ``tests/test_launch_forms.py`` holds them equal).
 
 Pinning: see each module's header and DESIGN.md §Oracle.
 """

@@ -6,15 +6,17 @@ INFRASTRUCTURE ONLY).
 tables below against ``oracle/pw_ref.py``; ``tests/test_oracle_pw.py`` checks, without a GPU,
 that the tables reach every launch form a contraction CAN reach, by enumerating sizes
 through the mirrors, and that the mirrors' split counts agree with the built library's
-``sgcn_pw_dw_ws_bytes``. Each mirror restates one C++ host function of
-``shift-gcn_amd/csrc/pwconv.hip``; when a chooser changes, its mirror (and, if a new form
-appears, the table) changes with it — the coverage test fails until the table reaches it.
+``sgcn_pw_dw_ws_bytes``. Each mirror restates one host function of
+``shift-gcn_amd/csrc/pw_forms.hpp`` (the entry points of ``pwconv.hip`` call those and
+nothing else decides a form); ``tests/test_launch_forms.py`` compiles that header into a host
+program and holds the mirrors, the constants below and the header's tile lists equal to it
+size by size. When a chooser changes, its mirror (and, if a new form appears, the table)
+changes with it — the coverage test fails until the table reaches it.
 
-Forms no size can reach (instantiated, never launched; kept — removing them is not this
-table's business):
+Forms no size can reach (paths inside kernels that are launched, or forms that are not
+built: every instantiated tile is reachable, ``tests/test_launch_forms.py``; kept — removing
+them is not this table's business):
 
-* ``pw_dw3_kernel`` 64 x 64, 128 x 64 and 64 x 128 (``dw3_cfg``'s first three rows):
-  ``use_dw3`` needs M * Nc >= 128 * 128, which M <= 128, Nc <= 64 (or the reverse) excludes.
 * ``pw_dw3_kernel`` 128 x 128 with a ragged tile: M <= 128, Nc <= 128 and M * Nc >= 16,384
   leave M = Nc = 128 only.
 * ``pw_dw_kernel`` 128 x 128 on its plain fast path: a full 128 x 128 tile needs M >= 128
@@ -30,7 +32,7 @@ table's business):
 from __future__ import annotations
 
 # --------------------------------------------------------------------------------------
-# mirrors of the host choosers (pwconv.hip)
+# mirrors of the host choosers (pw_forms.hpp)
 # --------------------------------------------------------------------------------------
 K_SMALL_M = 4            # kSmallM
 K_DW_BK = 64             # kDwBK: pw_dw_kernel positions per chunk
@@ -39,8 +41,8 @@ K_DWC_MAX_C = 4          # kDwcMaxC
 K_DW3_MIN = 128 * 128    # SGCN_DW3_MIN
 K_DW3_BKP_BIG = 16       # SGCN_DW3_BKP_BIG
 K_MASK_MAX_V = 64        # kMaskMaxV
-K_MAX_K = 256            # sgcn_pw_fwd: K <= 256
-K_EXTENT = 1 << 29       # operand extents (elements) the buffer descriptors accept
+K_MAX_K = 256            # kPwMaxK: sgcn_pw_fwd's K limit
+K_EXTENT = 1 << 29       # kPwMaxElems: operand extents (elements) the buffer ranges accept
 
 
 def _cdiv(a, b):
@@ -48,9 +50,9 @@ def _cdiv(a, b):
 
 
 def fwd_form(M, K, mask=False, x_rsign=0, y_rsign=0, w_mcontig=False, accumulate=False):
-    """``sgcn_pw_fwd``'s dispatch: (family, tile, staging, flags). family "smallm"
-    (``pw_fwd_smallm_kernel``, flags (AMC, ACCUM)) or "pwg" (``pwg_fwd_kernel``, staging
-    "ar" = A-resident or "db" = double-buffered, flags (MASK, XROT, AMC, ACCUM))."""
+    """``pw_fwd_form`` with ``sgcn_pw_fwd``'s flags: (family, tile, staging, flags). family
+    "smallm" (``pw_fwd_smallm_kernel``, flags (AMC, ACCUM)) or "pwg" (``pwg_fwd_kernel``,
+    staging "ar" = A-resident or "db" = double-buffered, flags (MASK, XROT, AMC, ACCUM))."""
     amc, acc = bool(w_mcontig), bool(accumulate)
     if M <= K_SMALL_M and not mask and x_rsign == 0 and y_rsign == 0:
         return ("smallm", None, None, (amc, acc))
@@ -63,7 +65,7 @@ def fwd_form(M, K, mask=False, x_rsign=0, y_rsign=0, w_mcontig=False, accumulate
 
 
 def tshift_form(M):
-    """``sgcn_pw_fwd_tshift``'s dispatch: the tile of its ``pwg_fwd_kernel<TSH>``."""
+    """``pw_tshift_form``: the tile of its ``pwg_fwd_kernel<TSH>``."""
     return (64, 256) if M <= 64 else (128, 256) if M <= 128 else (256, 128)
 
 
@@ -88,12 +90,6 @@ def use_dw3(M, Nc):
 
 def dw3_cfg(M, Nc):
     """``dw3_cfg``: (bm, bn, bkp, target)."""
-    if M <= 64 and Nc <= 64:
-        return (64, 64, 32, 2048)
-    if M <= 128 and Nc <= 64:
-        return (128, 64, 16, 1536)
-    if M <= 64 and Nc <= 128:
-        return (64, 128, 16, 1536)
     if M <= 128 and Nc <= 128:
         return (128, 128, 16, 1024)
     if Nc <= 128:
@@ -121,13 +117,13 @@ def dw_splits(M, Nc, B, N, tiles):
 
 
 def dw_plain(mask, g_rsign, x_rsign, g_extent=0, x_extent=0):
-    """The ``plain`` predicate of ``sgcn_pw_dw``."""
+    """``pw_dw_plain``."""
     return (not mask and g_rsign == 0 and x_rsign == 0 and g_extent < K_EXTENT and
             x_extent < K_EXTENT)
 
 
 def dw_form(B, M, Nc, T, V, mask=False, g_rsign=0, x_rsign=0, dbias=False):
-    """``sgcn_pw_dw``'s dispatch and split geometry, a dict:
+    """``pw_dw_form`` with ``sgcn_pw_dw``'s flags, and where its splits fall, a dict:
 
     family   "smallc" | "dw3" | "dw"
     tile     (bm, bn) (smallc: (NC,))

@@ -1194,7 +1194,8 @@ using namespace sgcn;
 template <class J, class L, class... A>
 static bool launch_plane(int T, int V, J&& ja, L&& loop, A... a) {
   const LaunchForm f = bn_form(T, V);
-  return f.kind == Kind::ja ? with_form<kJaForms>(f.nt, f.lpt, ja, a...) : with_consts(loop, a...);
+  if (f.kind == Kind::ja) return with_form<kJaForms>({f.nt, f.lpt}, ja, a...);
+  return with_consts(loop, a...);
 }
 
 extern "C" {

@@ -1,6 +1,7 @@
 // Runtime launch parameters -> template arguments. A launcher is one call:
 //
-//   const bool ok = with_form<kJaForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RELU, auto RES) {
+//   const Form form{f.nt, f.lpt};   // or a chooser's tile: with_form<kDw3Tiles>(f.tile, ...)
+//   const bool ok = with_form<kJaForms>(form, [&](auto NT, auto LPT, auto RELU, auto RES) {
 //     some_kernel<NT, LPT, RELU, RES><<<grid, int(NT), 0, st>>>(...);
 //   }, relu != 0, OneOf<0, 1, 2>{res});
 //
@@ -8,7 +9,9 @@
 // the listed forms x the flag values are instantiated; a value outside them launches
 // nothing and returns false (the entry point then returns SGCN_EINVAL).
 #pragma once
+#include <tuple>
 #include <type_traits>
+#include <utility>
 
 namespace sgcn {
 
@@ -51,16 +54,23 @@ bool with_consts(F&& f, A... a) {
   return bind_consts(f, Consts<>{}, a...);
 }
 
-// with_form<List>(nt, lpt, f, a...): f(NT, LPT, constants of a...) for the entry of List
-// (a constexpr Form[], launch_forms.hpp) that equals (nt, lpt)
-template <const auto& List, int I = 0, class F, class... A>
-bool with_form(int nt, int lpt, F&& f, A... a) {
+// with_form<List>(form, f, a...): f(constants of the fields of form, constants of a...) for
+// the entry of List that equals form. List is a constexpr array of a struct whose fields()
+// returns its members as a tuple (launch_forms.hpp Form, pw_forms.hpp tiles)
+template <const auto& List, size_t I, size_t... J>
+auto form_consts(std::index_sequence<J...>) {
+  return Consts<Const<std::get<J>(List[I].fields())>...>{};
+}
+template <const auto& List, size_t I = 0, class F, class... A>
+bool with_form(const std::remove_extent_t<std::remove_reference_t<decltype(List)>>& form, F&& f,
+               A... a) {
   if constexpr (I == std::extent_v<std::remove_reference_t<decltype(List)>>) {
     return false;
   } else {
-    if (List[I].nt == nt && List[I].lpt == lpt)
-      return bind_consts(f, Consts<Const<List[I].nt>, Const<List[I].lpt>>{}, a...);
-    return with_form<List, I + 1>(nt, lpt, f, a...);
+    constexpr size_t n = std::tuple_size_v<decltype(List[I].fields())>;
+    if (List[I].fields() == form.fields())
+      return bind_consts(f, form_consts<List, I>(std::make_index_sequence<n>{}), a...);
+    return with_form<List, I + 1>(form, f, a...);
   }
 }
 

@@ -6,6 +6,7 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <tuple>
 
 namespace sgcn {
 
@@ -192,6 +193,7 @@ inline LaunchForm bnin_form(int H, int W) {
 // ------------------------------------------------------------------------------------
 struct Form {
   int nt, lpt;
+  constexpr auto fields() const { return std::make_tuple(nt, lpt); }
 };
 // bn_form's ja: 512 threads only above kJaSplit floats, at least 17 per lane
 constexpr Form kJaForms[] = {{256, 8}, {256, 16}, {256, 24}, {256, 32}, {512, 24}, {512, 32}};

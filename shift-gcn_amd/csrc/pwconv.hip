@@ -28,13 +28,12 @@
 
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "pw_forms.hpp"
 
 namespace sgcn {
 namespace {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int kMaskMaxV = 64;      // joints per row supported by the LDS mask tables
 
 // A position-mapped plane operand: element (b, ch, n) with n = t*V + v (logical
 // position) lives at ptr[b*bstride + ch*cstride + (t*tstride)*V + rot(v, ch)], where
@@ -698,8 +697,6 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
 // ------------------------------------------------------------------------------------
 // dW (split-K over all positions)
 // ------------------------------------------------------------------------------------
-constexpr int kDwBK = 64;   // pw_dw_kernel positions per chunk
-
 struct DwArgs {
   Plane g;            // A operand rows m: G(b, m, n)
   Plane x;            // B operand rows n: X(b, c, n)
@@ -1168,11 +1165,6 @@ void launch_slab_reduce(const float* slab, const float* bslab, int S, int M, int
 // the per-lane sums are merged over the wave in a fixed xor order into slab[split]. Same
 // slab layout and reduction as pw_dw_kernel.
 // ------------------------------------------------------------------------------------
-#ifndef SGCN_DWC_ROWS
-#define SGCN_DWC_ROWS 16
-#endif
-constexpr int kDwcRows = SGCN_DWC_ROWS;   // G rows per wave
-constexpr int kDwcMaxC = 4;
 template <int NC, bool MASK>
 __global__ __launch_bounds__(256) void pw_dw_smallc_kernel(DwArgs p, int pos_per_split) {
   const int lane = threadIdx.x & 63;
@@ -1251,7 +1243,6 @@ __global__ __launch_bounds__(256) void pw_dw_smallc_kernel(DwArgs p, int pos_per
 // 16-byte read per k). HBM-bound on the K-row operand; the 64-row MFMA tile would stage
 // and multiply 61 rows of zeros. Same bias / ReLU / accumulate epilogue as pwg_fwd_kernel.
 // ------------------------------------------------------------------------------------
-constexpr int kSmallM = 4;
 template <bool AMC, bool ACCUM>
 __global__ __launch_bounds__(256) void pw_fwd_smallm_kernel(FwdArgs p) {
   SGCN_CRIT_PRIO();
@@ -1309,25 +1300,53 @@ __global__ __launch_bounds__(256) void pw_fwd_smallm_kernel(FwdArgs p) {
   }
 }
 // ------------------------------------------------------------------------------------
-// launch helpers
+// launch helpers (pw_forms.hpp chooses the family, tile and split geometry)
 // ------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN, bool AR = false>
-void launch_pwg(const FwdArgs& a, bool accum, hipStream_t st) {
+inline dim3 pwg_grid(const FwdArgs& a, const PwFwdTile& t) {
   const long long P = (long long)a.B * a.T * a.V;   // < 2^31 (checked by the caller)
-  dim3 grid((unsigned)((P + BN - 1) / BN), (a.M + BM - 1) / BM);
-  const bool mask = a.mask != nullptr, xrot = a.x.rsign != 0, amc = a.a_mcontig != 0;
-  with_consts([&](auto MASK, auto XROT, auto AMC, auto ACCUM) {
-    pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, AMC, ACCUM, false, AR>
-        <<<grid, 64 * WM * WN, 0, st>>>(a);
-  }, mask, xrot, amc, accum);
+  return dim3((unsigned)cdiv(P, t.bn), (unsigned)cdiv(a.M, t.bm));
 }
 
-template <int BM, int BN, int WM, int WN>
-void launch_pwg_tsh(const FwdArgs& a, hipStream_t st) {
-  const long long P = (long long)a.B * a.T * a.V;
-  dim3 grid((unsigned)((P + BN - 1) / BN), (a.M + BM - 1) / BM);
-  pwg_fwd_kernel<BM, BN, WM, WN, false, false, false, false, true>
-      <<<grid, 64 * WM * WN, 0, st>>>(a);
+// pwg_fwd_kernel on a tile of kPwFwdTiles (false: another tile, nothing launched)
+bool launch_pwg(const FwdArgs& a, const PwFwdTile& t, bool accum, hipStream_t st) {
+  return with_form<kPwFwdTiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AR, auto MASK,
+                                       auto XROT, auto AMC, auto ACCUM) {
+    pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, AMC, ACCUM, false, AR>
+        <<<pwg_grid(a, t), 64 * WM * WN, 0, st>>>(a);
+  }, a.mask != nullptr, a.x.rsign != 0, a.a_mcontig != 0, accum);
+}
+
+// ... with the fused temporal-shift operand, on a tile of kPwTshTiles
+bool launch_pwg_tsh(const FwdArgs& a, const PwFwdTile& t, hipStream_t st) {
+  return with_form<kPwTshTiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AR) {
+    pwg_fwd_kernel<BM, BN, WM, WN, false, false, false, false, true, AR>
+        <<<pwg_grid(a, t), 64 * WM * WN, 0, st>>>(a);
+  });
+}
+
+// The weight gradient's kernel on pw_dw_form's grid (a: slabs, chunks per split and byte
+// ranges set), one launcher per family; false: a tile outside its list, nothing launched
+bool launch_dwc(const DwArgs& a, const PwDwForm& f, hipStream_t st) {
+  return with_form<kDwcForms>({a.Nc}, [&](auto NC, auto MASK) {
+    pw_dw_smallc_kernel<NC, MASK><<<dim3(f.tiles, f.S), 256, 0, st>>>(a, f.per);
+  }, a.mask != nullptr);
+}
+
+bool launch_dw3(const DwArgs& a, const PwDwForm& f, hipStream_t st) {
+  return with_form<kDw3Tiles>(f.tile, [&](auto BM, auto BN, auto WM, auto WN, auto BKP, auto MASK,
+                                          auto GROT, auto XROT, auto BIAS) {
+    pw_dw3_kernel<BM, BN, WM, WN, BKP, MASK, GROT, XROT, BIAS>
+        <<<dim3(f.tiles, f.S), 64 * WM * WN, 0, st>>>(a);
+  }, a.mask != nullptr, a.g.rsign != 0, a.x.rsign != 0, a.bslab != nullptr);
+}
+
+// (operand form OP: 0 general, 1 plain = the buffer-descriptor fast path, 2 masked)
+bool launch_dw(const DwArgs& a, const PwDwForm& f, bool plain, hipStream_t st) {
+  return with_form<kDwTiles>(f.tile, [&](auto BM, auto BN, auto WM, auto WN, auto, auto OP) {
+    constexpr bool MASK = OP == 2;
+    pw_dw_kernel<BM, BN, WM, WN, MASK, OP == 1>
+        <<<dim3(f.tiles, f.S), 64 * WM * WN, MASK ? (size_t)a.V * BN * sizeof(float) : 0, st>>>(a);
+  }, OneOf<0, 1, 2>{a.mask ? 2 : plain});
 }
 
 // byte extent of a plane operand: one past its last addressed element
@@ -1338,111 +1357,29 @@ unsigned plane_bytes(long long bstride, long long cstride, int tstride, int B, i
   return (unsigned)(e * 4);
 }
 
-// split count for pw_dw3: ~target workgroups, slab <= 64 MiB, >= 1 chunk per split
-int dw3_splits(int M, int Nc, int P, int bkp, int tiles, int target) {
-  const int nch = (P + bkp - 1) / bkp;
-  int S = (target + tiles - 1) / tiles;
-  const long long cap = (64LL << 20) / (4LL * M * Nc);
-  if (S > cap) S = (int)cap;
-  if (S > nch) S = nch;
-  return S < 1 ? 1 : S;
+// what both forward entry points pass: weights (k- or m-contiguous), planes, sizes, divisors
+// and byte ranges; every optional pointer (mask, ts, xs) starts null
+FwdArgs fwd_args(const float* w, int w_mcontig, const float* bias, const Plane& x,
+                 const OutPlane& y, int relu, int B, int M, int K, int T, int V) {
+  FwdArgs a{};
+  a.A = w;
+  a.lda = w_mcontig ? M : K;
+  a.a_mcontig = w_mcontig;
+  a.bias = bias;
+  a.x = x;
+  a.y = y;
+  a.M = M;
+  a.K = K;
+  a.T = T;
+  a.V = V;
+  a.B = B;
+  fwd_divisors(a);
+  a.x_bytes = plane_bytes(x.bstride, x.cstride, x.tstride, B, K, T, V);
+  a.y_bytes = plane_bytes(y.bstride, y.cstride, y.tstride, B, M, T, V);
+  a.a_bytes = (unsigned)((long long)M * K * 4);
+  a.relu = relu ? 1 : 0;
+  return a;
 }
-
-struct Dw3Cfg {
-  int bm, bn, bkp, target;
-};
-// positions per chunk of the 256-row weight-gradient tiles (A/B knob: 8 halves their LDS,
-// 74 -> 37 KB at 256 x 256, leaving room on the CU for the critical path's kernels while
-// the side stream runs them)
-#ifndef SGCN_DW3_BKP_BIG
-#define SGCN_DW3_BKP_BIG 16
-#endif
-Dw3Cfg dw3_cfg(int M, int Nc) {
-  if (M <= 64 && Nc <= 64) return {64, 64, 32, 2048};
-  if (M <= 128 && Nc <= 64) return {128, 64, 16, 1536};
-  if (M <= 64 && Nc <= 128) return {64, 128, 16, 1536};
-  if (M <= 128 && Nc <= 128) return {128, 128, 16, 1024};
-  if (Nc <= 128) return {256, 128, SGCN_DW3_BKP_BIG, 512};
-  return {256, 256, SGCN_DW3_BKP_BIG, 512};
-}
-
-template <int BM, int BN, int WM, int WN, int BKP>
-void launch_dw3_t(const DwArgs& a, int S, int tiles, hipStream_t st) {
-  dim3 grid(tiles, S);
-  const bool mask = a.mask != nullptr, gr = a.g.rsign != 0, xr = a.x.rsign != 0,
-             bias = a.bslab != nullptr;
-  with_consts([&](auto MASK, auto GROT, auto XROT, auto BIAS) {
-    pw_dw3_kernel<BM, BN, WM, WN, BKP, MASK, GROT, XROT, BIAS><<<grid, 64 * WM * WN, 0, st>>>(a);
-  }, mask, gr, xr, bias);
-}
-
-// launches pw_dw3 for one dW into the slab workspace; returns the split count used
-int launch_dw3(const DwArgs& a0, hipStream_t st, float* ws, bool bias) {
-  DwArgs a = a0;
-  const Dw3Cfg c = dw3_cfg(a.M, a.Nc);
-  const int tiles = ((a.M + c.bm - 1) / c.bm) * ((a.Nc + c.bn - 1) / c.bn);
-  const int P = a.B * a.T * a.V;
-  const int S = dw3_splits(a.M, a.Nc, P, c.bkp, tiles, c.target);
-  const int nch = (P + c.bkp - 1) / c.bkp;
-  a.chunks_per_split = (nch + S - 1) / S;
-  a.slab = ws;
-  a.bslab = bias ? ws + (size_t)S * a.M * a.Nc : nullptr;
-  if (c.bm == 64 && c.bn == 64) launch_dw3_t<64, 64, 2, 2, 32>(a, S, tiles, st);
-  else if (c.bm == 128 && c.bn == 64) launch_dw3_t<128, 64, 2, 2, 16>(a, S, tiles, st);
-  else if (c.bm == 64 && c.bn == 128) launch_dw3_t<64, 128, 2, 2, 16>(a, S, tiles, st);
-  else if (c.bm == 128) launch_dw3_t<128, 128, 2, 2, 16>(a, S, tiles, st);
-  else if (c.bn == 128) launch_dw3_t<256, 128, 4, 2, SGCN_DW3_BKP_BIG>(a, S, tiles, st);
-  else launch_dw3_t<256, 256, 4, 2, SGCN_DW3_BKP_BIG>(a, S, tiles, st);
-  return S;
-}
-
-size_t dw3_ws_bytes(int B, int M, int Nc, int T, int V) {
-  const Dw3Cfg c = dw3_cfg(M, Nc);
-  const int tiles = ((M + c.bm - 1) / c.bm) * ((Nc + c.bn - 1) / c.bn);
-  const int S = dw3_splits(M, Nc, B * T * V, c.bkp, tiles, c.target);
-  return (size_t)S * ((size_t)M * Nc + M) * sizeof(float);
-}
-
-int dw_splits(int M, int Nc, int B, int N, int tiles) {
-  // ~512 workgroups (2 per CU at this kernel's register budget); slab <= 16 MiB
-  const int total = B * ((N + kDwBK - 1) / kDwBK);
-  int S = (512 + tiles - 1) / tiles;
-  const long long cap = (16LL << 20) / (4LL * M * Nc);
-  if (S > cap) S = (int)cap;
-  if (S > total) S = total;
-  return S < 1 ? 1 : S;
-}
-
-int dw_tile(int X) { return X > 64 ? 128 : 64; }
-
-// pw_dw_smallc_kernel: Nc <= 4; ~1,024 workgroups of 4 x 16 rows over position splits
-#ifndef SGCN_DWC
-#define SGCN_DWC 1
-#endif
-#ifndef SGCN_SMALLM
-#define SGCN_SMALLM 1
-#endif
-bool use_dwc(int Nc) { return SGCN_DWC && Nc <= kDwcMaxC; }
-#ifndef SGCN_PW_AR
-#define SGCN_PW_AR 1   // A/B knob: the A-resident K <= 64 forward tile (pwg_fwd_kernel AR)
-#endif
-int dwc_splits(int M, long long P) {
-  const int mg = (M + 4 * kDwcRows - 1) / (4 * kDwcRows);
-  long long S = (1024 + mg - 1) / mg;
-  const long long per = (P + S - 1) / S;
-  if (per < 256) S = (P + 255) / 256;   // at least four 64-position steps per split
-  return (int)(S < 1 ? 1 : S);
-}
-
-// pw_dw3 measured faster from 128x128 contractions up (tools/bench/pwbench: l5/l6 tcn,
-// l9 tcn/gcn), equal or slower on the 64-wide masked/rotated ones
-#ifndef SGCN_DW_PLAIN
-#define SGCN_DW_PLAIN 1   // A/B knob: the plain-operand fast path of pw_dw_kernel
-#endif
-#ifndef SGCN_DW3_MIN
-#define SGCN_DW3_MIN (128 * 128)
-#endif
-bool use_dw3(int M, int Nc) { return (long long)M * Nc >= SGCN_DW3_MIN; }
 
 }  // namespace
 }  // namespace sgcn
@@ -1456,44 +1393,28 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
                 const float* mask, float* y, long long y_bstride, long long y_cstride,
                 int y_tstride, int y_rsign, int relu, int accumulate, int B, int M, int K,
                 int T, int V, void* stream) {
-  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= 256 && T >= 0 && V > 0 && V < 32768);
+  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
   SGCN_REQUIRE(x_tstride >= 1 && y_tstride >= 1);
   SGCN_REQUIRE(x_rsign >= -1 && x_rsign <= 1 && y_rsign >= -1 && y_rsign <= 1);
   SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
   SGCN_REQUIRE(!mask || V <= kMaskMaxV);
   SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
   // operand extents must fit the 32-bit buffer ranges
-  SGCN_REQUIRE((long long)(B - 1) * x_bstride + (long long)K * x_cstride + (long long)T * x_tstride * V < (1LL << 29));
-  SGCN_REQUIRE((long long)(B - 1) * y_bstride + (long long)M * y_cstride + (long long)T * y_tstride * V < (1LL << 29));
+  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, x_tstride, B, K, T, V) < kPwMaxElems);
+  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, y_tstride, B, M, T, V) < kPwMaxElems);
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(w && x && y);
-  FwdArgs a{};   // value-initialised: every optional pointer (mask, ts) starts null
-  a.A = w;
-  a.lda = w_mcontig ? M : K;
-  a.a_mcontig = w_mcontig;
-  a.bias = bias;
-  a.x = {x, x_bstride, x_cstride, x_tstride, x_rsign};
+  FwdArgs a = fwd_args(w, w_mcontig, bias, {x, x_bstride, x_cstride, x_tstride, x_rsign},
+                       {y, y_bstride, y_cstride, y_tstride, y_rsign}, relu, B, M, K, T, V);
   a.mask = mask;
-  a.y = {y, y_bstride, y_cstride, y_tstride, y_rsign};
-  a.M = M;
-  a.K = K;
-  a.T = T;
-  a.V = V;
-  a.B = B;
-  fwd_divisors(a);
-  hipStream_t st = (hipStream_t)stream;
-  const bool rl = relu != 0;
-  bool ac = accumulate != 0;
-  a.x_bytes = plane_bytes(x_bstride, x_cstride, x_tstride, B, K, T, V);
-  a.y_bytes = plane_bytes(y_bstride, y_cstride, y_tstride, B, M, T, V);
-  a.a_bytes = (unsigned)((long long)M * K * 4);
   a.mask_bytes = mask ? (unsigned)(V * K * 4) : 0u;
-  a.relu = rl ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  bool ac = accumulate != 0;
 #ifdef SGCN_DIAG_X1B_BOUND
   // timing diagnostic only (results wrong): temporal_linear's input-gradient contraction
   // (W^T read m-contiguous, no bias / relu / accumulate) at M >= SGCN_DIAG_X1B_BOUND stores
   // nothing, i.e. the dAs write a fused shift_in backward epilogue would never make
-  if (w_mcontig && !bias && !rl && !ac && M >= SGCN_DIAG_X1B_BOUND) a.y_bytes = 0;
+  if (w_mcontig && !bias && !relu && !ac && M >= SGCN_DIAG_X1B_BOUND) a.y_bytes = 0;
 #endif
 #ifdef SGCN_DIAG_F1B_REAL
   // timing diagnostic only (results wrong): the gcn input-gradient contraction (see
@@ -1501,7 +1422,7 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
   // worth per element (the finish pass's x0 / residual-gradient / mask / BatchNorm-input
   // reads moved into the epilogue) while gcn_dx_finish does nothing: the realistic cost of
   // fusing that pass into this contraction (the bound alone drops the work)
-  if (!w_mcontig && !bias && !rl && !ac && M > kSmallM) {
+  if (!w_mcontig && !bias && !relu && !ac && M > kSmallM) {
     a.diag_f1b = 1;
     ac = true;
   }
@@ -1510,7 +1431,7 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
   // timing diagnostic only (results wrong): the Shift_gcn input-gradient contraction
   // (Linear_weight read k-contiguous as W^T, no bias / relu / accumulate) stores nothing,
   // and gcn_dx_finish reads no dXt (bn.hip): the whole dXt round trip free
-  if (!w_mcontig && !bias && !rl && !ac) a.y_bytes = 0;
+  if (!w_mcontig && !bias && !relu && !ac) a.y_bytes = 0;
 #endif
 #ifdef SGCN_DIAG_F2_BOUND
   // timing diagnostic only (tools/ab_variant.sh; results are wrong): the stride-2 residual
@@ -1518,27 +1439,17 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
   // sharing that read with the `down` conv (verdict r02, row f2) could save
   if (x_tstride == 2 && !ac) a.x_bytes = 0;
 #endif
-  if (M <= kSmallM && SGCN_SMALLM && !mask && x_rsign == 0 && y_rsign == 0) {
-    const unsigned grid = (unsigned)(((long long)B * T * V + 255) / 256);
-    if (w_mcontig) {
-      if (ac) pw_fwd_smallm_kernel<true, true><<<grid, 256, 0, st>>>(a);
-      else pw_fwd_smallm_kernel<true, false><<<grid, 256, 0, st>>>(a);
-    } else {
-      if (ac) pw_fwd_smallm_kernel<false, true><<<grid, 256, 0, st>>>(a);
-      else pw_fwd_smallm_kernel<false, false><<<grid, 256, 0, st>>>(a);
-    }
-  } else if (M <= 64) {
-    // 16 < K <= 64 (HBM-bound): A resident in LDS, one B buffer -> four workgroups per CU
-    // (one K stage, K <= 16, gains nothing from it: l1's K = 3 measured 4 % slower)
-    if (K > 16 && K <= 64 && SGCN_PW_AR) launch_pwg<64, 256, 2, 4, true>(a, ac, st);
-    else launch_pwg<64, 256, 2, 4>(a, ac, st);
+  const PwFwdForm f = pw_fwd_form(M, K, mask != nullptr, x_rsign, y_rsign);
+  bool ok;
+  if (f.smallm) {
+    const unsigned grid = (unsigned)cdiv((long long)B * T * V, 256);
+    ok = with_consts([&](auto AMC, auto ACCUM) {
+      pw_fwd_smallm_kernel<AMC, ACCUM><<<grid, 256, 0, st>>>(a);
+    }, w_mcontig != 0, ac);
+  } else {
+    ok = launch_pwg(a, f.tile, ac, st);
   }
-  // 64 < M <= 128: 128 x 128 tiles on 8 waves (32 x 64 per wave, twice the workgroups of
-  // the 128 x 256 tile): pw_fwd class -1.8 %, step +0.1..0.25 % same-box
-  // (profiles/r04_tiles/; 64 x 128 / 4-wave tiles at M <= 64 and 128 x 128 / 256 x 64
-  // tiles at M > 128 measured there too, not better)
-  else if (M <= 128) launch_pwg<128, 128, 4, 2>(a, ac, st);
-  else launch_pwg<256, 128, 4, 2>(a, ac, st);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;
 }
@@ -1551,14 +1462,14 @@ int sgcn_pw_fwd_tshift(const float* w, const float* bias, const float* x, long l
                        void* ws, size_t ws_bytes, float* y, long long y_bstride,
                        long long y_cstride, int relu, int two_row, int B, int M, int K, int T,
                        int V, void* stream) {
-  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= 256 && T >= 0 && V > 0 && V < 32768);
+  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
   SGCN_REQUIRE(two_row >= 0 && two_row <= 2);
   SGCN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr));
   SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
   SGCN_REQUIRE(x_cstride >= (long long)T * V && y_cstride >= (long long)T * V);
   SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
-  SGCN_REQUIRE((long long)(B - 1) * x_bstride + (long long)K * x_cstride + (long long)T * V < (1LL << 29));
-  SGCN_REQUIRE((long long)(B - 1) * y_bstride + (long long)M * y_cstride + (long long)T * V < (1LL << 29));
+  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, 1, B, K, T, V) < kPwMaxElems);
+  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, 1, B, M, T, V) < kPwMaxElems);
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(w && x && y && xpos && ypos && ws && ws_bytes >= sgcn_pw_tshift_ws_bytes(K));
   hipStream_t st = (hipStream_t)stream;
@@ -1566,43 +1477,17 @@ int sgcn_pw_fwd_tshift(const float* w, const float* bias, const float* x, long l
                                                      two_row, (int*)ws);
   tshift_two_row_flag_kernel<<<1, 256, 0, st>>>(K, (int*)ws);
   SGCN_LAUNCH_CHECK();
-  FwdArgs a{};
-  a.A = w;
-  a.lda = K;
-  a.a_mcontig = 0;
-  a.bias = bias;
-  a.x = {x, x_bstride, x_cstride, 1, 0};
-  a.mask = nullptr;
+  FwdArgs a = fwd_args(w, 0, bias, {x, x_bstride, x_cstride, 1, 0},
+                       {y, y_bstride, y_cstride, 1, 0}, relu, B, M, K, T, V);
   a.ts = (const int*)ws;
   a.xs = x_shifted;
-  a.y = {y, y_bstride, y_cstride, 1, 0};
-  a.M = M;
-  a.K = K;
-  a.T = T;
-  a.V = V;
-  a.B = B;
-  fwd_divisors(a);
-  a.x_bytes = plane_bytes(x_bstride, x_cstride, 1, B, K, T, V);
-  a.y_bytes = plane_bytes(y_bstride, y_cstride, 1, B, M, T, V);
-  a.a_bytes = (unsigned)((long long)M * K * 4);
-  a.mask_bytes = 0u;
-  a.relu = relu ? 1 : 0;
-  // (the plain path's 128 x 128 tile at 64 < M <= 128 measured no better for this operand,
-  // profiles/r06_x1/tshbench_tile128x128.txt)
-  if (M <= 64) launch_pwg_tsh<64, 256, 2, 4>(a, st);
-  else if (M <= 128) launch_pwg_tsh<128, 256, 2, 4>(a, st);
-  else launch_pwg_tsh<256, 128, 4, 2>(a, st);
+  SGCN_REQUIRE(launch_pwg_tsh(a, pw_tshift_form(M), st));
   SGCN_LAUNCH_CHECK();
   return 0;
 }
 
 size_t sgcn_pw_dw_ws_bytes(int B, int M, int Nc, int T, int V) {
-  if (use_dwc(Nc))
-    return (size_t)dwc_splits(M, (long long)B * T * V) * ((size_t)M * Nc + M) * sizeof(float);
-  if (use_dw3(M, Nc)) return dw3_ws_bytes(B, M, Nc, T, V);
-  const int tiles = ((M + dw_tile(M) - 1) / dw_tile(M)) * ((Nc + dw_tile(Nc) - 1) / dw_tile(Nc));
-  const int S = dw_splits(M, Nc, B, T * V, tiles);
-  return (size_t)S * ((size_t)M * Nc + M) * sizeof(float);
+  return pw_dw_form(B, M, Nc, T, V).ws_bytes;
 }
 
 int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_tstride,
@@ -1614,76 +1499,36 @@ int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_t
   SGCN_REQUIRE(g && x && dw && ws && g_tstride >= 1 && x_tstride >= 1);
   SGCN_REQUIRE(g_rsign >= -1 && g_rsign <= 1 && x_rsign >= -1 && x_rsign <= 1);
   SGCN_REQUIRE(!mask || V <= kMaskMaxV);
-  SGCN_REQUIRE(ws_bytes >= sgcn_pw_dw_ws_bytes(B, M, Nc, T, V));
+  const PwDwForm f = pw_dw_form(B, M, Nc, T, V);
+  SGCN_REQUIRE(ws_bytes >= f.ws_bytes);
   SGCN_REQUIRE(g_cstride * (long long)M < (1LL << 31) && x_cstride * (long long)Nc < (1LL << 31));
-  DwArgs a{};   // value-initialised: every optional pointer (mask, ts) starts null
-  a.g = {g, g_bstride, g_cstride, g_tstride, g_rsign};
-  a.x = {x, x_bstride, x_cstride, x_tstride, x_rsign};
-  a.mask = mask;
-  a.M = M;
-  a.Nc = Nc;
-  a.T = T;
-  a.V = V;
-  a.B = B;
-  hipStream_t st = (hipStream_t)stream;
-  int S;
-  if (use_dwc(Nc)) {
-    const long long P = (long long)B * T * V;
-    S = dwc_splits(M, P);
-    a.slab = (float*)ws;
-    a.bslab = dbias ? (float*)ws + (size_t)S * M * Nc : nullptr;
-    const int per = (int)((P + S - 1) / S);
-    dim3 grid((M + 4 * kDwcRows - 1) / (4 * kDwcRows), S);
-    const bool ok = with_consts([&](auto NC, auto MASK) {
-      pw_dw_smallc_kernel<NC, MASK><<<grid, 256, 0, st>>>(a, per);
-    }, OneOf<1, 2, 3, 4>{Nc}, mask != nullptr);
-    SGCN_REQUIRE(ok);
-  } else if (use_dw3(M, Nc)) {
+  const long long ge = pw_extent(g_bstride, g_cstride, g_tstride, B, M, T, V);
+  const long long xe = pw_extent(x_bstride, x_cstride, x_tstride, B, Nc, T, V);
+  const bool plain = pw_dw_plain(mask != nullptr, g_rsign, x_rsign, ge, xe);
+  if (f.family == DwFamily::dw3) SGCN_REQUIRE(ge < kPwMaxElems && xe < kPwMaxElems);
+  DwArgs a{{g, g_bstride, g_cstride, g_tstride, g_rsign},
+           {x, x_bstride, x_cstride, x_tstride, x_rsign}, mask, (float*)ws, nullptr, M, Nc, T, V,
+           B, f.per};   // (the byte ranges start 0)
+  if (dbias) a.bslab = a.slab + (size_t)f.S * M * Nc;
+  if (f.family == DwFamily::dw3 || plain) {   // the byte ranges of their buffer loads
     a.g_bytes = plane_bytes(g_bstride, g_cstride, g_tstride, B, M, T, V);
     a.x_bytes = plane_bytes(x_bstride, x_cstride, x_tstride, B, Nc, T, V);
     a.mask_bytes = mask ? (unsigned)(V * Nc * 4) : 0u;
-    SGCN_REQUIRE((long long)(B - 1) * g_bstride + (long long)M * g_cstride + (long long)T * g_tstride * V < (1LL << 29));
-    SGCN_REQUIRE((long long)(B - 1) * x_bstride + (long long)Nc * x_cstride + (long long)T * x_tstride * V < (1LL << 29));
-    S = launch_dw3(a, st, (float*)ws, dbias != nullptr);
-    a.slab = (float*)ws;
-    a.bslab = dbias ? (float*)ws + (size_t)S * M * Nc : nullptr;
-  } else {
-    const int bm = dw_tile(M), bn = dw_tile(Nc);
-    const int tiles = ((M + bm - 1) / bm) * ((Nc + bn - 1) / bn);
-    const int N = T * V;
-    S = dw_splits(M, Nc, B, N, tiles);
-    const int total = B * ((N + kDwBK - 1) / kDwBK);
-    a.slab = (float*)ws;
-    a.bslab = dbias ? (float*)ws + (size_t)S * M * Nc : nullptr;
-    a.chunks_per_split = (total + S - 1) / S;
-    dim3 grid(tiles, S);
-    // the buffer-descriptor fast path: plain operands whose byte extents fit 32 bits
-    const long long ge = (long long)(B - 1) * g_bstride + (long long)M * g_cstride +
-                         (long long)T * g_tstride * V;
-    const long long xe = (long long)(B - 1) * x_bstride + (long long)Nc * x_cstride +
-                         (long long)T * x_tstride * V;
-    const bool plain = !mask && g_rsign == 0 && x_rsign == 0 && SGCN_DW_PLAIN &&
-                       ge < (1LL << 29) && xe < (1LL << 29);
-    if (plain) {
-      a.g_bytes = plane_bytes(g_bstride, g_cstride, g_tstride, B, M, T, V);
-      a.x_bytes = plane_bytes(x_bstride, x_cstride, x_tstride, B, Nc, T, V);
-    }
-    auto tile = [&](auto BM, auto BN, auto MASK, auto PLAIN) {
-      constexpr int WM = BM / 32;
-      pw_dw_kernel<BM, BN, WM, 2, MASK, PLAIN>
-          <<<grid, 64 * WM * 2, MASK ? (size_t)V * BN * sizeof(float) : 0, st>>>(a);
-    };
-    const OneOf<64, 128> tm{bm}, tn{bn};
+  }
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = true;
+  if (f.family == DwFamily::smallc) ok = launch_dwc(a, f, st);
+  else if (f.family == DwFamily::dw3) ok = launch_dw3(a, f, st);
+  else
 #ifdef SGCN_DIAG_DW64_SKIP
     // timing bound only: the 64 x 64 weight gradients are not computed (the slabs keep
     // whatever they held), the most a dX + dW fusion at C = 64 could remove
-    if (bm == 64 && bn == 64 && plain) {} else
+    if (!(f.tile.bm == 64 && f.tile.bn == 64 && plain))
 #endif
-    if (mask) with_consts(tile, tm, tn, Const<true>{}, Const<false>{});
-    else with_consts(tile, tm, tn, Const<false>{}, plain);
-  }
+    ok = launch_dw(a, f, plain, st);
+  SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
-  launch_slab_reduce(a.slab, a.bslab, S, M, Nc, dw, dw_transpose, dw_accumulate, dbias,
+  launch_slab_reduce(a.slab, a.bslab, f.S, M, Nc, dw, dw_transpose, dw_accumulate, dbias,
                      dbias_accumulate, st);
   SGCN_LAUNCH_CHECK();
   return 0;

@@ -1295,7 +1295,7 @@ struct RaArgs {
 // flags AFFINE, RELU, BNP, GP, GBN, GBD (dispatch.hpp); false: nothing launched
 template <const auto& Forms, class... A>
 bool launch_ra(const LaunchForm& f, const RaArgs& a, hipStream_t st, A... flags) {
-  return with_form<Forms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto RELU, auto BNP,
+  return with_form<Forms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto AFFINE, auto RELU, auto BNP,
                                            auto GP, auto GBN, auto GBD) {
     tshift_bwd_ra_kernel<NT, LPT, AFFINE, RELU, BNP, GP, GBN, GBD>
         <<<a.B * a.C, int(NT), ra_lds_bytes(a.H, a.W, NT, GBN), st>>>(
@@ -1329,14 +1329,14 @@ int sgcn_tshift_fwd(const float* in, float* out, const float* xpos, const float*
   bool ok;
   if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
     const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
+    ok = with_form<kPadFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
       tshift_fwd_pad_kernel<NT, LPT, 0, AFFINE, STATS><<<B * C, int(NT), lds, st>>>(
           in, out, xpos, ypos, in_scale, in_shift, ps, C, H, W, Ho, stride, ah);
     }, aff, stats);
   } else if (f.kind == Kind::lds) {
     // EPT = LPT (the output plane is never larger than the staged input plane)
     const size_t lds = (size_t)H * W * sizeof(float);
-    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
+    ok = with_form<kLdsFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto AFFINE, auto STATS) {
       tshift_fwd_lds_kernel<NT, LPT, LPT, AFFINE, STATS><<<B * C, int(NT), lds, st>>>(
           in, out, xpos, ypos, in_scale, in_shift, ps, C, H, W, Ho, stride, ah);
     }, aff, stats);
@@ -1371,14 +1371,14 @@ int sgcn_tshift_fwd_pre(const float* z, float* out, const float* xpos, const flo
   bool ok;
   if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
     const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES) {
+    ok = with_form<kPadFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto RES) {
       tshift_fwd_pad_kernel<NT, LPT, 1, true, false, RES><<<B * C, int(NT), lds, st>>>(
           z, out, xpos, ypos, in_scale, in_shift, nullptr, C, H, W, Ho, stride, ah, pre_scale,
           pre_shift, r, r_scale, r_shift);
     }, res);
   } else {
     const size_t lds = (size_t)H * W * sizeof(float);
-    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES) {
+    ok = with_form<kLdsFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto RES) {
       tshift_fwd_pre_kernel<NT, LPT, RES><<<B * C, int(NT), lds, st>>>(
           z, out, xpos, ypos, pre_scale, pre_shift, r, r_scale, r_shift, in_scale, in_shift, C,
           H, W, Ho, stride, ah);
@@ -1410,14 +1410,14 @@ int sgcn_tshift_fwd_tail(const float* in, float* out, const float* xpos, const f
   bool ok;
   if (f.kind == Kind::pad) {   // padded joint-aligned kernel (W <= 64)
     const size_t lds = (size_t)(ra_pad_floats(H, W) + 1) * sizeof(float);
-    ok = with_form<kPadFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES, auto GOUT) {
+    ok = with_form<kPadFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto RES, auto GOUT) {
       tshift_fwd_pad_kernel<NT, LPT, 2, false, false, RES, GOUT><<<B * C, int(NT), lds, st>>>(
           in, out, xpos, ypos, post_scale, post_shift, nullptr, C, H, W, Ho, stride, ah, nullptr,
           nullptr, r, r_scale, r_shift, gather_m, out_gathered);
     }, res, go);
   } else {
     const size_t lds = (size_t)H * W * sizeof(float);
-    ok = with_form<kLdsFwdForms>(f.nt, f.lpt, [&](auto NT, auto LPT, auto RES, auto GOUT) {
+    ok = with_form<kLdsFwdForms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto RES, auto GOUT) {
       tshift_fwd_tail_kernel<NT, LPT, RES, GOUT><<<B * C, int(NT), lds, st>>>(
           in, out, xpos, ypos, post_scale, post_shift, r, r_scale, r_shift, gather_m,
           out_gathered, C, H, W, Ho, stride, ah);

@@ -168,7 +168,7 @@ def test_dw_table_reaches_every_reachable_family_and_tile():
     want = ({("dw", t) for t in itertools.product((64, 128), repeat=2)} |
             {("dw3", (128, 128)), ("dw3", (256, 128)), ("dw3", (256, 256))} |
             {("smallc", (n,)) for n in (1, 2, 3, 4)})
-    assert reach == want      # dw3_cfg's 64 x 64, 128 x 64, 64 x 128 rows: unreachable
+    assert reach == want      # no smaller pw_dw3_kernel tile: use_dw3 needs M * Nc >= 128 * 128
     table = {_dw_key(pc.dw_form(*c)) for c in pc.DW_TABLE}
     assert table == want
     assert set(pc.DW_FLAG_SHAPES) <= want

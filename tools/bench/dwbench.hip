@@ -105,8 +105,11 @@ void big(hipStream_t st, float* x, float* y, float* mask, float* ws, float* dw1,
       // product: 128 x 128, 2 x 2 waves, BKP 16, 1024 workgroups (reference for the diffs)
       {
         DwArgs a = d;
-        const int S = launch_dw3(a, st, ws, false);
-        auto L = [&]() { launch_dw3(a, st, ws, false); };
+        const PwDwForm f = pw_dw_form(B, M, K, T, V);
+        const int S = f.S;
+        a.slab = ws;
+        a.chunks_per_split = f.per;
+        auto L = [&]() { launch_dw3(a, f, st); };
         const float uk = timeit(L, st, 20);
         launch_slab_reduce(ws, nullptr, S, M, K, dw1, 0, 0, nullptr, 0, st);
         CK(hipStreamSynchronize(st));
@@ -156,9 +159,12 @@ void huge(hipStream_t st, float* x, float* y, float* ws, float* dw1, float* dw2)
     Ctx c{st, ws, nullptr, dw1, by, name, fl};
     {
       DwArgs a = d;
-      const int S = launch_dw3(a, st, ws, false);
+      const PwDwForm f = pw_dw_form(B, M, K, T, V);
+      const int S = f.S;
+      a.slab = ws;
+      a.chunks_per_split = f.per;
       auto L = [&]() {
-        launch_dw3(a, st, ws, false);
+        launch_dw3(a, f, st);
         launch_slab_reduce(ws, nullptr, S, M, K, dw1, 0, 0, nullptr, 0, st);
       };
       for (int r = 0; r < 2; ++r) {

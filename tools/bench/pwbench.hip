@@ -74,7 +74,13 @@ template <int BM, int BN, int WM, int WN, bool AR = false>
 void fwd_variant(const Shape& s, const FwdArgs& a, hipStream_t st, const float* yref,
                  double fl, double by) {
   if (a.M > BM || (AR && a.K > 64)) return;
-  auto L = [&]() { launch_pwg<BM, BN, WM, WN, AR>(a, false, st); };
+  const dim3 grid = pwg_grid(a, {BM, BN, WM, WN, AR});
+  auto L = [&]() {
+    with_consts([&](auto MASK, auto XROT) {
+      pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, false, false, false, AR>
+          <<<grid, 64 * WM * WN, 0, st>>>(a);
+    }, a.mask != nullptr, a.x.rsign != 0);
+  };
   float us = timeit(L, st, 20);
   const size_t n = (size_t)s.B * s.M * s.T * s.V;
   printf("%-20s fwd %3dx%3d w%dx%d%s         %8.1f us  %6.1f TF/s  %6.2f TB/s  %s\n", s.name,
@@ -203,7 +209,7 @@ int main(int argc, char** argv) {
       d.x = {x, s.K * N, N, 1, s.rot ? 1 : 0};
       d.mask = s.mask ? mask : nullptr;
       d.M = s.M; d.Nc = s.K; d.T = s.T; d.V = s.V; d.B = s.B;
-      const int bm = dw_tile(s.M), bn = dw_tile(s.K);
+      const int bm = dw_tile(s.M, s.K).bm, bn = dw_tile(s.M, s.K).bn;
       const int tiles = ((s.M + bm - 1) / bm) * ((s.K + bn - 1) / bn);
       const int S0 = dw_splits(s.M, s.K, s.B, (int)N, tiles);
       if (bm == 128 && bn == 128) dw_variant<128, 128, 4, 2>("dw product 128x128", s, d, S0, st, ws, nullptr, dw1, fl, by);
@@ -212,10 +218,15 @@ int main(int argc, char** argv) {
       d3.g_bytes = plane_bytes(d.g.bstride, d.g.cstride, 1, s.B, s.M, s.T, s.V);
       d3.x_bytes = plane_bytes(d.x.bstride, d.x.cstride, 1, s.B, s.K, s.T, s.V);
       d3.mask_bytes = s.mask ? (unsigned)(s.V * s.K * 4) : 0u;
-      int S3 = 0;
+      // pw_dw3 where the product takes it
+      const PwDwForm f3 = pw_dw_form(s.B, s.M, s.K, s.T, s.V);
+      if (f3.family != DwFamily::dw3) continue;
+      d3.slab = ws;
+      d3.chunks_per_split = f3.per;
+      const int S3 = f3.S;
       const int MN = s.M * s.K;
       auto L3 = [&]() {
-        S3 = launch_dw3(d3, st, ws, false);
+        launch_dw3(d3, f3, st);
         launch_slab_reduce(ws, nullptr, S3, s.M, s.K, dw2, 0, 0, nullptr, 0, st);
       };
       float us = timeit(L3, st, 10);
