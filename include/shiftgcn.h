@@ -212,6 +212,20 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
                 int y_tstride, int y_rsign, int relu, int accumulate, int B, int M, int K,
                 int T, int V, void* stream);
 
+/* Eval-mode inference contraction with bf16 operands (additive, ABI stays 25):
+ *   Y[b][m][out(n,m)] = act( sum_k bf16(A[m][k]) * bf16(X(b,k,n)) + bias[m] ),  n < T*V
+ * sgcn_pw_fwd with mask = NULL, x_rsign = 0, accumulate = 0, except that both operands are
+ * rounded to bf16 (round to nearest even) while they are staged; w and x stay fp32 in
+ * memory. Products are exact in fp32 (v_mfma_f32_32x32x16_bf16); the sums, the bias add,
+ * ReLU and the y_rsign / y_tstride store mapping are sgcn_pw_fwd's, in fp32. 1 <= K <= 256,
+ * any M >= 1; B == 0 returns 0 without a launch; everything sgcn_pw_fwd rejects is
+ * rejected with SGCN_EINVAL. Subnormal, infinite and NaN operands are not pinned. No
+ * backward is offered through it: eval blocks that cannot be back-propagated only. */
+int sgcn_pw_fwd_bf16(const float* w, int w_mcontig, const float* bias, const float* x,
+                     long long x_bstride, long long x_cstride, int x_tstride, float* y,
+                     long long y_bstride, long long y_cstride, int y_tstride, int y_rsign,
+                     int relu, int B, int M, int K, int T, int V, void* stream);
+
 /* Shift_tcn's shift_in fused into its temporal_linear (shift_gcn.py:66-70):
  *   Y[b][m][n] = act( sum_k w[m*K + k] * S_k(b, n) + bias[m] ),
  *   S_k = shift_k(in_scale[k] * X[b][k] + in_shift[k])   (stride-1 temporal shift,

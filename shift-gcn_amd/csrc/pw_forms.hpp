@@ -68,6 +68,22 @@ inline PwFwdForm pw_fwd_form(int M, int K, bool mask, int x_rsign, int y_rsign) 
 inline PwFwdTile pw_tshift_form(int M) { return kPwTshTiles[M <= 64 ? 0 : (M <= 128 ? 1 : 2)]; }
 
 // ------------------------------------------------------------------------------------
+// sgcn_pw_fwd_bf16 (eval-mode inference, bf16 operands on v_mfma_f32_32x32x16_bf16):
+// BM x BN tile on WM x WN waves, 32 k per LDS stage. The fp32 forward's tile footprints; M
+// past 256 takes more row blocks of the 256-row tile. K does not enter the choice.
+// ------------------------------------------------------------------------------------
+struct PwBf16Tile {
+  int bm, bn, wm, wn;
+  constexpr auto fields() const { return std::make_tuple(bm, bn, wm, wn); }
+};
+constexpr int kPwBf16BK = 32;                  // k per stage (two MFMA k-steps of 16)
+constexpr PwBf16Tile kPwBf16Tiles[] = {{64, 256, 2, 4}, {128, 128, 4, 2}, {256, 128, 4, 2}};
+inline PwBf16Tile pw_fwd_bf16_form(int M, int K) {
+  (void)K;
+  return kPwBf16Tiles[M <= 64 ? 0 : (M <= 128 ? 1 : 2)];
+}
+
+// ------------------------------------------------------------------------------------
 // sgcn_pw_dw: family, tile and split-K geometry
 // ------------------------------------------------------------------------------------
 struct PwDwTile {

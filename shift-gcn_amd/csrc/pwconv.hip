@@ -695,6 +695,282 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
 }
 
 // ------------------------------------------------------------------------------------
+// Eval-mode inference forward with bf16 operands (sgcn_pw_fwd_bf16): the plain contraction
+// (no mask, no operand rotation, no accumulate) on v_mfma_f32_32x32x16_bf16. Both operands
+// stay fp32 in memory and are rounded to bf16 (round to nearest even, the hardware's packed
+// convert) on their way into LDS; products of two bf16 values are exact in fp32 and the
+// accumulator, bias add, ReLU and stores are fp32, as in pwg_fwd_kernel.
+//
+// LDS holds bf16 in 16-byte slots of 8 consecutive k: a stage (32 k) of an operand is four
+// groups g of [rows][8 k], so the fragment of lane (r = lane & 31, h = lane >> 5) for the
+// MFMA k-step s is ONE slot, (group 2s + h, row r): 32 lanes read 512 contiguous bytes.
+//  * X: a thread owns one position column and eight consecutive k rows of it (coalesced
+//    loads along the positions), converts them and writes one slot.
+//  * A, k-contiguous (Conv2d weights): a thread owns a k pair of a row (16 lanes read 128
+//    contiguous bytes), writes one dword; the groups are 2 slots apart from a multiple of
+//    the bank count so the four groups a wave writes land on different banks.
+//  * A, m-contiguous (Linear_weight): as X, a thread owns a row m and eight k.
+// Rows k >= K are out of the descriptor range for BOTH operands (zeros in LDS; a k past K
+// is never read from memory), rows m >= M and columns past P likewise. Two stages are
+// double-buffered with one barrier each; the epilogue is pwg_fwd_kernel's (the C/D map of
+// the 32 x 32 forms does not depend on the operand type), copied so that the fp32
+// kernels' code stays what it was.
+// Not pinned: subnormal, infinite and NaN operands.
+// ------------------------------------------------------------------------------------
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+typedef u32x4 __attribute__((may_alias)) lds_slot;
+typedef unsigned __attribute__((may_alias)) lds_word;
+typedef float __attribute__((may_alias)) lds_float;
+
+template <int BM, int BN, int WM, int WN, bool AMC>
+__global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_bf16_kernel(FwdArgs p) {
+  SGCN_CRIT_PRIO();
+  constexpr int NT = 64 * WM * WN;
+  constexpr int BK = kPwBf16BK, KG = BK / 8;   // k-groups of 8 per stage
+  constexpr int MI = BM / WM / 32;
+  constexpr int NJ = BN / WN / 32;
+  constexpr int AG = BM + 2, BG = BN;          // slots per group
+  constexpr int ASZ = KG * AG, BSZ = KG * BG;  // slots per stage buffer
+  // X: NT / BN groups per pass
+  constexpr int BGS = NT / BN, B_IT = KG / BGS;
+  // A k-contiguous: 16 k pairs x NT / 16 rows per pass; m-contiguous: NT / BM groups per pass
+  constexpr int A_ROWS = NT / 16, A_IT = BM / A_ROWS;
+  constexpr int AGS = NT / BM, AM_IT = (KG + AGS - 1) / AGS;
+  static_assert(MI >= 1 && NJ >= 1 && BK == 32, "bad tile");
+  static_assert(NT % BN == 0 && KG % BGS == 0 && B_IT >= 1, "bad tile (X staging)");
+  static_assert(BM % A_ROWS == 0 && NT % BM == 0 && BM % 64 == 0, "bad tile (A staging)");
+  constexpr int NW = WM * WN;
+  constexpr int RB = WM * 16;      // epilogue: staged rows per pass
+  constexpr int CQ = BN / 64;      // 64-column groups per row
+  constexpr int RPW = RB / NW;     // rows per wave per pass
+  static_assert(BN % 64 == 0 && RB % NW == 0, "epilogue staging");
+  constexpr int OPS = 2 * (ASZ + BSZ), EPS = RB * BN / 4;
+  __shared__ lds_slot smem[OPS > EPS ? OPS : EPS];
+  lds_slot* const As = smem;                   // [2][KG][AG]
+  lds_slot* const Bs = smem + 2 * ASZ;         // [2][KG][BG]
+  __shared__ float bias_s[BM];
+  __shared__ int rot_s[BM];
+  __shared__ unsigned ycol_s[BN];   // per tile column: byte offset of (b, t) in Y
+  __shared__ int v_s[BN];           // per tile column: joint v
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wid / WN, wn = wid - (wid / WN) * WN;
+  const int V = p.V, N = p.T * V, K = p.K, M = p.M;
+  const int P = p.B * N;                 // < 2^31 (host-checked)
+  const int p0 = xcd_tile<SGCN_PW_XCD>(blockIdx.x, gridDim.x) * BN;
+  const int m0 = blockIdx.y * BM;
+  const auto xr = make_rsrc(p.x.ptr, p.x_bytes);
+  const auto ar = make_rsrc(p.A, p.a_bytes);
+
+  for (int i = tid; i < BM; i += NT) {
+    bias_s[i] = (p.bias && m0 + i < M) ? p.bias[m0 + i] : 0.f;
+    rot_s[i] = p.y.rsign ? pmod(p.y.rsign * (m0 + i), V) : 0;
+  }
+
+  // ---- X column of this thread (fixed for the tile) ----
+  const int nb = tid % BN;
+  const int bg0 = __builtin_amdgcn_readfirstlane(tid / BN);
+  unsigned xcol = p.x_bytes;   // out of range: loads return 0
+  {
+    const int pc = p0 + nb;
+    unsigned ycol = p.y_bytes;   // out of range: stores dropped
+    int vv = 0;
+    if (pc < P) {
+      const int b = fdiv(pc, p.divN_m, p.divN_s);
+      const int n = pc - b * N;
+      const int t = fdiv(n, p.divV_m, p.divV_s);
+      vv = n - t * V;
+      // 32-bit offsets: every term is at most the operand's byte extent (< 2^32, host-checked)
+      xcol = ((unsigned)b * (unsigned)p.x.bstride + (unsigned)t * (unsigned)(p.x.tstride * V) +
+              (unsigned)vv) * 4u;
+      ycol = ((unsigned)b * (unsigned)p.y.bstride + (unsigned)t * (unsigned)(p.y.tstride * V)) * 4u;
+    }
+    if (tid < BN) {
+      ycol_s[nb] = ycol;
+      v_s[nb] = vv;
+    }
+  }
+  const unsigned xcs4 = (unsigned)(p.x.cstride * 4);
+
+  // ---- A elements of this thread ----
+  const int lda = p.lda;
+  // k-contiguous: the pair (2 kp, 2 kp + 1) of rows am + it * A_ROWS
+  const int kp = tid & 15, am = tid >> 4;
+  const unsigned avoff = (unsigned)(((m0 + am) * lda + 2 * kp) * 4);
+  const int kspan = K - 2 * kp;   // the pair's elements are inside the row while k0 < kspan (- 1)
+  // m-contiguous: row amc, groups ag0 + it * AGS
+  const int amc = tid % BM;
+  const int ag0 = __builtin_amdgcn_readfirstlane(tid / BM);
+  const unsigned amvoff = m0 + amc < M ? (unsigned)((m0 + amc) * 4) : p.a_bytes;
+
+  float rb[B_IT][8];
+  float ra[AMC ? AM_IT * 8 : A_IT * 2];
+  auto load_stage = [&](int k0) {
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int row = k0 + (bg0 + it * BGS) * 8 + j;   // uniform
+        rb[it][j] = bload_pol<SGCN_PW_XPOL>(xr, row < K ? xcol : p.x_bytes,
+                                            (unsigned)min(row, K - 1) * xcs4);
+      }
+    if constexpr (AMC) {
+#pragma unroll
+      for (int it = 0; it < AM_IT; ++it) {
+        const int g = ag0 + it * AGS;   // uniform
+        if (g >= KG) break;             // more waves than groups (BM = 64)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int row = k0 + g * 8 + j;
+          ra[it * 8 + j] = bload_pol<SGCN_PW_APOL>(ar, row < K ? amvoff : p.a_bytes,
+                                                   (unsigned)(min(row, K - 1) * lda * 4));
+        }
+      }
+    } else {
+      // a k past K would alias the next row: such a lane's load goes out of the range (and
+      // so does a row past M: its offset is at least the extent)
+#pragma unroll
+      for (int it = 0; it < A_IT; ++it) {
+        const unsigned vo = avoff + (unsigned)(it * A_ROWS * lda * 4);
+        ra[2 * it] = bload_pol<SGCN_PW_APOL>(ar, k0 < kspan ? vo : p.a_bytes, (unsigned)(k0 * 4));
+        ra[2 * it + 1] =
+            bload_pol<SGCN_PW_APOL>(ar, k0 < kspan - 1 ? vo + 4u : p.a_bytes, (unsigned)(k0 * 4));
+      }
+    }
+  };
+  auto pack8 = [](const float* v) {
+    bf16x8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = (__bf16)v[j];
+    return __builtin_bit_cast(u32x4, r);
+  };
+  auto store_stage = [&](int buf) {
+#pragma unroll
+    for (int it = 0; it < B_IT; ++it)
+      Bs[buf * BSZ + (bg0 + it * BGS) * BG + nb] = pack8(rb[it]);
+    if constexpr (AMC) {
+#pragma unroll
+      for (int it = 0; it < AM_IT; ++it) {
+        const int g = ag0 + it * AGS;
+        if (g < KG) As[buf * ASZ + g * AG + amc] = pack8(&ra[it * 8]);
+      }
+    } else {
+      lds_word* const Aw = reinterpret_cast<lds_word*>(As + buf * ASZ);
+#pragma unroll
+      for (int it = 0; it < A_IT; ++it) {
+        bf16x2 r;
+        r[0] = (__bf16)ra[2 * it];
+        r[1] = (__bf16)ra[2 * it + 1];
+        Aw[((kp >> 2) * AG + am + it * A_ROWS) * 4 + (kp & 3)] = __builtin_bit_cast(unsigned, r);
+      }
+    }
+  };
+
+  f32x16 acc[MI][NJ];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x16{};
+
+  const int kl = lane >> 5, cl = lane & 31;
+  const int nstage = (K + BK - 1) / BK;
+  load_stage(0);
+  store_stage(0);
+  __syncthreads();
+  for (int s = 0; s < nstage; ++s) {
+    const int cur = s & 1;
+    if (s + 1 < nstage) load_stage((s + 1) * BK);
+    const lds_slot* __restrict__ Ar = As + cur * ASZ + kl * AG + wm * (BM / WM) + cl;
+    const lds_slot* __restrict__ Br = Bs + cur * BSZ + kl * BG + wn * (BN / WN) + cl;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 af[MI], bf[NJ];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) af[i] = __builtin_bit_cast(bf16x8, Ar[2 * kk * AG + i * 32]);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) bf[j] = __builtin_bit_cast(bf16x8, Br[2 * kk * BG + j * 32]);
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+    }
+    if (s + 1 < nstage) store_stage(cur ^ 1);
+    __syncthreads();
+  }
+
+  // ---- epilogue (pwg_fwd_kernel's: the tile staged through LDS in passes of 16 rows per
+  // wave band, each wave then stores whole tile rows, every 128-B line completed at once) ----
+  lds_float* const smemf = reinterpret_cast<lds_float*>(smem);
+  const auto yr = make_rsrc(p.y.ptr, p.y_bytes);
+  const unsigned ycs4 = (unsigned)(p.y.cstride * 4);
+  unsigned ycolq[CQ];
+  int vq[CQ];
+#pragma unroll
+  for (int q = 0; q < CQ; ++q) {
+    ycolq[q] = ycol_s[lane + 64 * q];
+    vq[q] = v_s[lane + 64 * q];
+  }
+  const bool rotated = p.y.rsign != 0;
+  auto row_of = [&](int i, int h, int k) {   // tile row of this wave's k-th row of a pass
+    const int lr = wid + k * NW;
+    return (lr >> 4) * (BM / WM) + i * 32 + 16 * h + (lr & 15);   // uniform
+  };
+  auto epilogue = [&](auto relu_tag, auto rot_tag) {
+    constexpr bool RELU = decltype(relu_tag)::value;
+    constexpr bool ROT = decltype(rot_tag)::value;
+    auto voff_of = [&](int trow, int q) {
+      int vo = vq[q];
+      if constexpr (ROT) {   // shift_out rotation of the stored joint
+        vo += rot_s[trow];
+        vo = vo >= V ? vo - V : vo;
+      }
+      return vo;
+    };
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int rr = 0; rr < 8; ++rr) {
+            const int r = 8 * h + rr;
+            const int lr = wm * 16 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * kl;
+            smemf[lr * BN + wn * (BN / WN) + j * 32 + cl] = acc[i][j][r];
+          }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < RPW; ++k) {
+          const int lr = wid + k * NW;
+          const int trow = row_of(i, h, k);
+          if (m0 + trow >= M) break;   // rows past M (they increase with k)
+          const float bv = bias_s[trow];
+          const unsigned soff = (unsigned)(m0 + trow) * ycs4;
+#pragma unroll
+          for (int q = 0; q < CQ; ++q) {
+            const unsigned voff = ycolq[q] + (unsigned)(voff_of(trow, q) * 4);
+            float val = smemf[lr * BN + lane + 64 * q] + bv;
+            if (RELU) val = fmaxf(val, 0.f);
+            bstore(yr, val, voff, soff);
+          }
+        }
+        __syncthreads();
+      }
+  };
+  if (rotated) {
+    if (p.relu) epilogue(std::true_type{}, std::true_type{});
+    else epilogue(std::false_type{}, std::true_type{});
+  } else {
+    if (p.relu) epilogue(std::true_type{}, std::false_type{});
+    else epilogue(std::false_type{}, std::false_type{});
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // dW (split-K over all positions)
 // ------------------------------------------------------------------------------------
 struct DwArgs {
@@ -1324,6 +1600,15 @@ bool launch_pwg_tsh(const FwdArgs& a, const PwFwdTile& t, hipStream_t st) {
   });
 }
 
+// pwg_fwd_bf16_kernel on a tile of kPwBf16Tiles
+bool launch_pwg_bf16(const FwdArgs& a, const PwBf16Tile& t, hipStream_t st) {
+  const long long P = (long long)a.B * a.T * a.V;   // < 2^31 (checked by the caller)
+  const dim3 grid((unsigned)cdiv(P, t.bn), (unsigned)cdiv(a.M, t.bm));
+  return with_form<kPwBf16Tiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AMC) {
+    pwg_fwd_bf16_kernel<BM, BN, WM, WN, AMC><<<grid, 64 * WM * WN, 0, st>>>(a);
+  }, a.a_mcontig != 0);
+}
+
 // The weight gradient's kernel on pw_dw_form's grid (a: slabs, chunks per split and byte
 // ranges set), one launcher per family; false: a tile outside its list, nothing launched
 bool launch_dwc(const DwArgs& a, const PwDwForm& f, hipStream_t st) {
@@ -1450,6 +1735,27 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
     ok = launch_pwg(a, f.tile, ac, st);
   }
   SGCN_REQUIRE(ok);
+  SGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+int sgcn_pw_fwd_bf16(const float* w, int w_mcontig, const float* bias, const float* x,
+                     long long x_bstride, long long x_cstride, int x_tstride, float* y,
+                     long long y_bstride, long long y_cstride, int y_tstride, int y_rsign,
+                     int relu, int B, int M, int K, int T, int V, void* stream) {
+  // sgcn_pw_fwd's checks (mask = NULL, x_rsign = 0)
+  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
+  SGCN_REQUIRE(x_tstride >= 1 && y_tstride >= 1);
+  SGCN_REQUIRE(y_rsign >= -1 && y_rsign <= 1);
+  SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
+  SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
+  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, x_tstride, B, K, T, V) < kPwMaxElems);
+  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, y_tstride, B, M, T, V) < kPwMaxElems);
+  if (B == 0 || T == 0) return 0;
+  SGCN_REQUIRE(w && x && y);
+  const FwdArgs a = fwd_args(w, w_mcontig, bias, {x, x_bstride, x_cstride, x_tstride, 0},
+                             {y, y_bstride, y_cstride, y_tstride, y_rsign}, relu, B, M, K, T, V);
+  SGCN_REQUIRE(launch_pwg_bf16(a, pw_fwd_bf16_form(M, K), (hipStream_t)stream));
   SGCN_LAUNCH_CHECK();
   return 0;
 }

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, fused, ops
 
 MODALITIES = ("joint", "bone", "joint_motion", "bone_motion")   # inference_pipeline.py:25
 ENSEMBLE_WEIGHTS_DEFAULT = (0.6, 0.6, 0.4, 0.4)                  # inference_pipeline.py:24
@@ -102,8 +102,12 @@ class Ensemble(nn.Module):
     ``logits`` the float64 fused logits (N, num_class)."""
 
     def __init__(self, models, weights=ENSEMBLE_WEIGHTS_DEFAULT,
-                 bone_pairs=MEDIAPIPE_BONE_PAIRS):
+                 bone_pairs=MEDIAPIPE_BONE_PAIRS, precision=None):
         super().__init__()
+        # the members' eval precision ("fp32" / "bf16", fused.eval_precision); None: the
+        # process default (SGCN_EVAL_PRECISION, else "fp32")
+        self.precision = fused.check_precision(
+            fused.EVAL_PRECISION if precision is None else precision)
         if len(models) != 4 or len(weights) != 4:
             raise ValueError("one model and one weight per stream: " + ", ".join(MODALITIES))
         self.models = nn.ModuleList(models)
@@ -152,13 +156,24 @@ class Ensemble(nn.Module):
                                     data_bn=self._data_bn_coef())
         acc = torch.zeros(N, self.models[0].fc.out_features, device=joint.device,
                           dtype=torch.float64)
+        with fused.eval_precision(self.precision):
+            outs = self._run_members(streams, joint.device, N, M)
+        for k, logits in enumerate(outs):
+            acc = acc + (logits * self.alpha32[k]).double()
+        # softmax exactly as inference_pipeline.py:364-365 (max-shifted exp in float64)
+        e = torch.exp(acc - acc.max(dim=1, keepdim=True).values)
+        scores = e[:, 1] / e.sum(dim=1)
+        return scores, acc
+
+    def _run_members(self, streams, device, N, M):
+        """The four members' logits on their modality planes (inside the precision setting)."""
         if ENS_STREAMS:
             # the four models are independent until the fused score: each runs on its own
             # stream (forked from and joined back into the current one; works inside a
             # hipGraph capture), so their MFMA- and HBM-bound phases overlap; the logits
             # are then accumulated in stream order as before
-            cur = torch.cuda.current_stream(joint.device)
-            subs = _ens_streams(joint.device)
+            cur = torch.cuda.current_stream(device)
+            subs = _ens_streams(device)
             outs = []
             for m, xs, st in zip(self.models, streams, subs):
                 st.wait_stream(cur)
@@ -169,12 +184,7 @@ class Ensemble(nn.Module):
                 cur.wait_stream(st)
         else:
             outs = [m.forward_planes(xs, N, M) for m, xs in zip(self.models, streams)]
-        for k, logits in enumerate(outs):
-            acc = acc + (logits * self.alpha32[k]).double()
-        # softmax exactly as inference_pipeline.py:364-365 (max-shifted exp in float64)
-        e = torch.exp(acc - acc.max(dim=1, keepdim=True).values)
-        scores = e[:, 1] / e.sum(dim=1)
-        return scores, acc
+        return outs
 
 
 # submodule (re)registrations anywhere: EnsembleGraph re-lists the ensemble's modules

@@ -302,7 +302,8 @@ def gcn_forward(mod, x0, training, off=False, gathered=None, prepared=None):
         D0 = _empty(B, Cout, T, V, like=x0)
         down = _OffPath(off, x0)
         with down:
-            ops.pw_fwd(conv.weight, False, conv.bias, PV(x0), PV(D0), Cout, Cin, T, V)
+            _eval_pw_fwd(training, conv.weight, False, conv.bias, PV(x0), PV(D0), Cout, Cin, T,
+                         V)
             if training:
                 dst = ops.bn_finalize(ops.moments(D0, False), B, Cout, T * V, bn)
             else:
@@ -315,7 +316,8 @@ def gcn_forward(mod, x0, training, off=False, gathered=None, prepared=None):
     Z = _empty(B, Cout, T, V, like=x0)
     # Z is stored BEFORE shift_out (plain contraction stores) and the BatchNorm kernels
     # apply the joint rotation in their addressing (per_joint = 3)
-    ops.pw_fwd(mod.Linear_weight, True, mod.Linear_bias, PV(xg), PV(Z), Cout, Cin, T, V)
+    _eval_pw_fwd(training, mod.Linear_weight, True, mod.Linear_bias, PV(xg), PV(Z), Cout, Cin, T,
+                 V)
     if training:
         zst = ops.bn_finalize(ops.moments(Z, 3), B, Cout * V, T, mod.bn, perm_V=V)
     else:
@@ -482,7 +484,7 @@ def convbn_infer_folded(mod, x):
     To = (T - 1) // mod.stride + 1
     w, b = folded_conv_bn(conv, mod.bn)
     R = _empty(B, Cout, To, V, like=x)
-    ops.pw_fwd(w, False, b, PV(x, mod.stride), PV(R), Cout, Cin, To, V)
+    _eval_pw_fwd(False, w, False, b, PV(x, mod.stride), PV(R), Cout, Cin, To, V)
     return R
 
 
@@ -497,16 +499,17 @@ def gcn_infer_z(mod, x0, gathered=None, prepared=None):
     else:
         xg = ops.gcn_gather(x0, _mask_of(mod, prepared))
     Z = _empty(B, Cout, T, V, like=x0)
-    ops.pw_fwd(mod.Linear_weight, True, mod.Linear_bias, PV(xg), PV(Z, 1, +1), Cout, Cin, T, V)
+    _eval_pw_fwd(False, mod.Linear_weight, True, mod.Linear_bias, PV(xg), PV(Z, 1, +1), Cout, Cin,
+                 T, V)
     zst = ops.bn_eval_coef(mod.bn, Cout * V, perm_V=V)
     if mod.has_down:
         conv, bn = mod.down[0], mod.down[1]
         D0 = _empty(B, Cout, T, V, like=x0)
         if EVAL_FOLD:   # down.1 folded into down.0: the residual needs no affine
             w, b = folded_conv_bn(conv, bn)
-            ops.pw_fwd(w, False, b, PV(x0), PV(D0), Cout, Cin, T, V)
+            _eval_pw_fwd(False, w, False, b, PV(x0), PV(D0), Cout, Cin, T, V)
             return Z, zst, D0, None
-        ops.pw_fwd(conv.weight, False, conv.bias, PV(x0), PV(D0), Cout, Cin, T, V)
+        _eval_pw_fwd(False, conv.weight, False, conv.bias, PV(x0), PV(D0), Cout, Cin, T, V)
         return Z, zst, D0, ops.bn_eval_coef(bn, Cout)
     return Z, zst, x0, None
 
@@ -532,7 +535,7 @@ def tcn_core_forward(mod, H, training, h_moments=None, tail=None, pre=None):
     if pre is not None:   # inference: H = relu(BN1d(Z) + res) formed while staging
         As = ops.tshift_fwd_pre(pre[0], si.xpos.detach(), si.ypos.detach(), si.stride, pre[1],
                                 pre[2], pre[3], ast)
-        ops.pw_fwd(tl.weight, False, tl.bias, PV(As), PV(R), Cout, C, T, V, relu=True)
+        _eval_pw_fwd(training, tl.weight, False, tl.bias, PV(As), PV(R), Cout, C, T, V, relu=True)
     elif tshift_fused(C) and tail is None:
         # shift_in (with Shift_tcn.bn's apply) formed in the contraction's operand staging,
         # never read back; also stored from the same registers for the weight gradient
@@ -541,7 +544,7 @@ def tcn_core_forward(mod, H, training, h_moments=None, tail=None, pre=None):
                           PV(R), Cout, C, T, V, relu=True, x_shifted=As, two_row=TSHIFT_TWO_ROW)
     else:
         As = ops.tshift_fwd(H, si.xpos.detach(), si.ypos.detach(), si.stride, affine=ast)
-        ops.pw_fwd(tl.weight, False, tl.bias, PV(As), PV(R), Cout, C, T, V, relu=True)
+        _eval_pw_fwd(training, tl.weight, False, tl.bias, PV(As), PV(R), Cout, C, T, V, relu=True)
     To = T // stride
     if tail is not None:
         # inference: bn2 (eval) + residual + ReLU (+ next gather) fused into shift_out
@@ -628,7 +631,7 @@ def convbn_core_forward(mod, x, training):
     s_t = mod.stride
     To = (T - 1) // s_t + 1
     Rc = _empty(B, Cout, To, V, like=x)
-    ops.pw_fwd(conv.weight, False, conv.bias, PV(x, s_t), PV(Rc), Cout, Cin, To, V)
+    _eval_pw_fwd(training, conv.weight, False, conv.bias, PV(x, s_t), PV(Rc), Cout, Cin, To, V)
     if training:
         rst = ops.bn_finalize(ops.moments(Rc, False), B, Cout, To * V, bn)
     else:
@@ -928,6 +931,66 @@ ASYNC_DW = int(os.environ.get("SGCN_ASYNC_DW", "1"))
 # pool's expanded gradient is never written (_unit_backward, _unit_dy_planes). Bit-identical.
 # A/B knob: 0 = every consumer re-reads the output for its mask, as before.
 PREMASK = int(os.environ.get("SGCN_PREMASK", "1"))
+
+# Eval-mode inference precision (DESIGN.md §Reduced-precision inference). "bf16": the forward
+# contractions of eval blocks that no backward can follow round both operands to bf16 while
+# staging them (ops.pw_fwd_bf16); sums, bias, ReLU, stores and every other kernel stay fp32.
+# "fp32" (the default): every launch is the one made without this setting. Opt-in per thread
+# with eval_precision(); SGCN_EVAL_PRECISION is the process default (read once, here).
+EVAL_PRECISIONS = ("fp32", "bf16")
+
+
+def check_precision(precision):
+    if precision not in EVAL_PRECISIONS:
+        raise ValueError(f"eval precision must be one of {EVAL_PRECISIONS}, got {precision!r}")
+    return precision
+
+
+EVAL_PRECISION = check_precision(os.environ.get("SGCN_EVAL_PRECISION", "fp32"))
+# the contractions that take the bf16 path: K >= 32 (l1's K = 3 contractions on raw
+# coordinates are HBM-bound and stay fp32) and more output rows than the small-M kernel's
+BF16_MIN_K = 32
+
+
+class _Precision(threading.local):
+    value = EVAL_PRECISION
+
+
+_PRECISION = _Precision()
+
+
+class eval_precision:
+    """``with eval_precision("bf16"): model(x)`` — the eval-mode inference precision of the
+    calling thread inside the block ("fp32" or "bf16"); restores the previous one on exit.
+    Only eval-mode blocks that cannot be back-propagated through (torch.no_grad(), or
+    nothing requires grad) change; training and any differentiable forward stay fp32."""
+
+    def __init__(self, precision):
+        self.precision = check_precision(precision)
+        self.prev = None
+
+    def __enter__(self):
+        self.prev = _PRECISION.value
+        _PRECISION.value = self.precision
+        return self
+
+    def __exit__(self, *exc):
+        _PRECISION.value = self.prev
+        return False
+
+
+def current_eval_precision():
+    return _PRECISION.value
+
+
+def _eval_pw_fwd(training, w, w_mcontig, bias, x, out, M, K, T, V, relu=False):
+    """A forward contraction an eval block may run with bf16 operands: ops.pw_fwd_bf16 when
+    the thread's precision is "bf16", the block is in eval mode, no backward can follow
+    (_INFER.active, run_block) and the shape is one that gains; else ops.pw_fwd as ever."""
+    if (_PRECISION.value == "bf16" and not training and _INFER.active and K >= BF16_MIN_K and
+            M > ops.SMALL_M):
+        return ops.pw_fwd_bf16(w, w_mcontig, bias, x, out, M, K, T, V, relu=relu)
+    return ops.pw_fwd(w, w_mcontig, bias, x, out, M, K, T, V, relu=relu)
 
 
 def block_params(module):

@@ -615,6 +615,36 @@ def pw_fwd(w, w_mcontig, bias, x: PlaneView, out: PlaneView, M, K, T, V, mask=No
     return out.t
 
 
+SMALL_M = 4   # csrc/pw_forms.hpp kSmallM: output rows of the fp32 small-M forward kernel
+
+
+def pw_fwd_bf16(w, w_mcontig, bias, x: PlaneView, out: PlaneView, M, K, T, V, relu=False):
+    """The twin of pw_fwd for eval-mode inference (sgcn_pw_fwd_bf16): both operands are
+    rounded to bf16 while staged, products and sums stay fp32. Plain X operand only (no
+    mask, no rotation), no accumulate; ``out`` may carry a rotation and a time stride."""
+    check_input(w, "weight")
+    _opt(bias, "bias")
+    if x.rsign != 0:
+        raise ValueError("pw_fwd_bf16: the X operand is a plain plane")
+    B = x.t.shape[0]
+    lib = _lib.load()
+    P = B * T * V
+    bc = _batch_chunk([(x, K), (out, M)], B, T, V)
+    det = (f"M{M} K{K} T{T} V{V} yrot{out.rsign} ts{x.tstride}{out.tstride} "
+           f"mc{int(w_mcontig)}")
+    with _timed("pw_fwd_bf16", 2.0 * P * M * K, 4.0 * P * (M + K), x.t, det):
+        for b0 in range(0, B, bc):
+            nb = min(bc, B - b0)
+            rc = lib.sgcn_pw_fwd_bf16(_ptr(w), int(w_mcontig), _ptr(bias),
+                                      x.t.data_ptr() + 4 * b0 * x.bstride, x.bstride,
+                                      x.cstride, x.tstride,
+                                      out.t.data_ptr() + 4 * b0 * out.bstride,
+                                      out.bstride, out.cstride, out.tstride, out.rsign,
+                                      int(relu), nb, M, K, T, V, _stream(x.t))
+            _lib.check(rc, "sgcn_pw_fwd_bf16")
+    return out.t
+
+
 def pw_dw(g: PlaneView, x: PlaneView, dw, M, Nc, T, V, mask=None, transpose=False,
           accumulate=False, dbias=None, dbias_accumulate=False):
     check_input(dw, "dw")
