@@ -51,7 +51,9 @@ extern "C" {
  * pool gradient's (N*M, C) plane values).
  * 25: the sequence pipeline: sgcn_window_normalize (every sliding window of a landmark
  * sequence cut, padded and pre-normalised on the device) and sgcn_window_aggregate (window
- * scores averaged per frame). */
+ * scores averaged per frame). Added within 25 (additive, no entry changed):
+ * sgcn_pw_fwd_bf16 (eval-mode bf16-operand contractions) and sgcn_clip_augment (the feeder's
+ * training augmentations on the device). */
 int sgcn_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -454,6 +456,43 @@ int sgcn_window_normalize(const float* seq, const int* table, float* out, int n_
  * scores: (n_windows) float64;  per_frame: (total_frames) float64. */
 int sgcn_window_aggregate(const double* scores, const int* table, double* per_frame,
                           int n_windows, int total_frames, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Feeder augmentations (feeders/feeder.py:74-90, feeders/tools.py:32-117)
+ * ---------------------------------------------------------------------------------- */
+#define SGCN_AUG_NORMALIZE 1   /* flags bit 0: (x - mean_map) / std_map */
+#define SGCN_AUG_MOVE 2        /* flags bit 1: random_move on channels 0 and 1 */
+#define SGCN_AUG_MAX_NODES 9   /* random_move nodes per sample (move_time <= 8) */
+
+/* Replaces the per-sample augmentation chain of `Feeder.__getitem__` (normalization,
+ * tools.random_shift, tools.random_choose / tools.auto_pading, tools.random_move) for a
+ * whole batch in one launch (added within ABI 25). The random draws are made by the caller
+ * (shiftgcn.augment.ClipAugment.draw, the reference's streams in the reference's order) and
+ * arrive as per-sample device tables:
+ * in   : (B, C, T, V, M) raw clips;  out: (B, C, T_out, V, M), must not alias in;
+ * frame_map: (B, 3) int32 {src0, dst0, count}: output frame t in [dst0, dst0 + count) is
+ *   input frame src0 + t - dst0 (normalised when bit 0 is set); every other output frame is
+ *   0 before the move. It is the shift composed with the window's crop or pad. Rows are
+ *   clamped: a frame whose source lies outside [0, T) is written as 0, nothing is read or
+ *   written out of bounds.
+ * nodes: (B, 1 + max_nodes) int32 {num_node, node[0..max_nodes)} and
+ * move : (B, 4, max_nodes) float64 rows {A (degrees), S, T_x, T_y} at the nodes (bit 1).
+ *   Output frame t in [node[i], node[i+1]) takes a, s, t_x, t_y =
+ *   np.linspace(X[i], X[i+1], node[i+1] - node[i])[t - node[i]] (i*step and +start rounded
+ *   separately, the last element of a segment is X[i+1], one element gives X[i]),
+ *   a = a * pi / 180, and channels 0 and 1 of every element of the frame become
+ *   [cos a*s, -sin a*s; sin a*s, cos a*s] (x, y) + (t_x, t_y) in float64, rounded to float32
+ *   once. A frame in no segment gets the zero matrix, as the reference's np.zeros(T) does.
+ *   Channels >= 2 are not touched by the move.
+ * mean, std: (C, V) float32 maps (bit 0), applied as IEEE float32 subtract then divide.
+ * Without bit 1 the result is bit-exact with the reference; with it, it differs by the
+ * device's float64 sin/cos and the evaluation order of the 2x2 product.
+ * mean/std may be NULL without bit 0, nodes/move without bit 1. EINVAL: a NULL required
+ * pointer, a dimension < 1, unknown flag bits, bit 1 with C < 2 or max_nodes outside
+ * [2, SGCN_AUG_MAX_NODES], V*M > 2^26. */
+int sgcn_clip_augment(const float* in, float* out, const int* frame_map, const int* nodes,
+                      const double* move, const float* mean, const float* std, int B, int C,
+                      int T, int T_out, int V, int M, int max_nodes, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Model head / tail of the training step (shift_gcn.py:193-216)

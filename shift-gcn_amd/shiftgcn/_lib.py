@@ -82,6 +82,7 @@ SIGNATURES = {
     "sgcn_window_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                                    _P]),
     "sgcn_window_aggregate": (_I, [_P, _P, _P, _I, _I, _P]),
+    "sgcn_clip_augment": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sgcn_tshift_bwd_gbn": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     "sgcn_bn_bwd_finalize_gbn": (_I, [_P, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I,
@@ -120,7 +121,13 @@ def _open(path):
     if abi != ABI_VERSION:
         raise NativeLibraryError(f"{path}: ABI version {abi} != {ABI_VERSION}; rebuild it")
     for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # an entry added within the ABI version (sgcn_pw_fwd_bf16, sgcn_clip_augment)
+            raise NativeLibraryError(
+                f"{path} (ABI {abi}) has no {name}: it was built from an older tree; "
+                "rebuild it") from None
         fn.restype = res
         fn.argtypes = args
     return lib

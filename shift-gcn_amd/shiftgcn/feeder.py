@@ -7,14 +7,19 @@ device without stalling the compute stream.
   and ``main.py``'s eval loop work unchanged). The clip array ``(N, C, T, V, M)`` float32
   is memory-mapped (``use_mmap``); the ``(sample_name, label)`` pickle is read with a
   restricted unpickler that resolves NO globals (plain lists/tuples/str/int only), so a
-  label file cannot execute code. The augmentations of ``feeders/tools.py`` are off in
-  every reference config (``config/*/train_*.yaml``) and are not provided.
+  label file cannot execute code. ``Feeder`` itself takes no augmentation flag (they are
+  off in every reference config, ``config/*/train_*.yaml``); the augmentations of
+  ``feeders/tools.py`` are :class:`shiftgcn.augment.AugmentedFeeder` (same constructor, the
+  flags accepted) and run on the device when it feeds a :class:`DeviceBatchLoader`.
 * :class:`DeviceBatchLoader` — the training/eval batch stream on the GPU: the next
   batches' rows are gathered from the mmap into pinned host buffers by a worker thread
   (numpy's gather releases the GIL) and copied host->device on a dedicated copy stream,
   ``depth`` batches ahead; the compute stream waits on an event per batch, never on the
   host. Batch order is identical to ``DataLoader(feeder, batch_size, shuffle, drop_last)``
-  under the same global torch seed (``main.py:235-251``).
+  under the same global torch seed (``main.py:235-251``). With ``augment`` (a
+  :class:`shiftgcn.augment.ClipAugment`, or the feeder's own) the worker also computes each
+  sample's valid-frame extent and makes the reference's random draws, and one launch on the
+  copy stream writes the augmented batch that is handed out.
 """
 from __future__ import annotations
 
@@ -60,8 +65,8 @@ class Feeder(torch.utils.data.Dataset):
                  use_mmap=True):
         if random_choose or random_shift or random_move or window_size > 0 or normalization:
             raise NotImplementedError(
-                "feeder augmentations (random_choose/shift/move, window_size, normalization) "
-                "are not provided: every reference config runs with them off")
+                "Feeder takes no augmentation flag (random_choose/shift/move, window_size, "
+                "normalization): use shiftgcn.augment.AugmentedFeeder, which accepts them")
         self.debug = debug
         self.data_path = data_path
         self.label_path = label_path
@@ -118,11 +123,23 @@ def loader_order(n, batch_size, shuffle, drop_last, generator=None):
 
 class DeviceBatchLoader:
     """Iterate ``(clips, labels, indices)`` batches of a :class:`Feeder` on ``device``,
-    prefetched ``depth`` batches ahead (pinned staging + a copy stream + events)."""
+    prefetched ``depth`` batches ahead (pinned staging + a copy stream + events).
+
+    ``augment``: a :class:`shiftgcn.augment.ClipAugment`; left ``None``, the feeder's own
+    ``.augment`` is used when it has one (``AugmentedFeeder``). The clips handed out are then
+    the augmented ``(B, C, T_out, V, M)`` float32 batch: a single worker draws batch after
+    batch in loader order, so under one seed every sample equals ``augment.apply_host`` run
+    sequentially over the same indices (bit for bit without ``random_move``, to float64
+    evaluation differences with it). The worker draws ahead of the consumer: an iterator
+    that is closed early has already advanced the streams by the batches it had prefetched.
+    With ``world_size > 1`` each rank's ``ClipAugment``
+    draws for its own shard only: the augmentation streams differ per rank, as they do
+    across the reference's DataLoader workers under ``nn.DataParallel``."""
 
     def __init__(self, feeder: Feeder, batch_size, shuffle=False, drop_last=False,
-                 device="cuda", depth=2, generator=None, rank=0, world_size=1):
+                 device="cuda", depth=2, generator=None, rank=0, world_size=1, augment=None):
         self.feeder = feeder
+        self.augment = augment if augment is not None else getattr(feeder, "augment", None)
         self.batch_size = int(batch_size)
         # data-parallel shard: every rank draws the same global order (same seed) of
         # batch_size*world_size batches and takes its slice of each
@@ -158,6 +175,11 @@ class DeviceBatchLoader:
         hx = [torch.empty(shape, dtype=torch.float32, pin_memory=cuda) for _ in range(nbuf)]
         hy = [torch.empty((self.batch_size,), dtype=torch.int64, pin_memory=cuda)
               for _ in range(nbuf)]
+        aug = self.augment
+        if aug is not None:   # the draws of batch k, packed next to its staging buffer
+            from .augment import AugmentParams
+            hp = [torch.empty((AugmentParams.packed_nbytes(self.batch_size),),
+                              dtype=torch.uint8, pin_memory=cuda) for _ in range(nbuf)]
         free, ready, stop = queue.Queue(), queue.Queue(), threading.Event()
         for k in range(nbuf):
             free.put(k)
@@ -171,7 +193,14 @@ class DeviceBatchLoader:
                     ia = np.asarray(idx, dtype=np.int64)
                     np.take(data, ia, axis=0, out=hx[k].numpy()[:len(idx)])
                     hy[k].numpy()[:len(idx)] = labels[ia]
-                    ready.put((k, idx))
+                    p = None
+                    if aug is not None:
+                        # the reference's draws need each (normalised) clip's extent first
+                        raw = hx[k].numpy()[:len(idx)]
+                        ext = aug.batch_extents(raw) if aug.needs_extents else len(idx)
+                        p = aug.draw(ext, raw.shape[2])
+                        p.pack(hp[k].numpy())
+                    ready.put((k, idx, p))
             except BaseException as e:   # re-raised in the consumer
                 ready.put(e)
 
@@ -194,17 +223,28 @@ class DeviceBatchLoader:
             item = ready.get()
             if isinstance(item, BaseException):
                 raise item
-            k, idx = item
+            k, idx, p = item
             b = len(idx)
             if cuda:
                 with torch.cuda.stream(copy_stream):
                     x = hx[k][:b].to(self.device, non_blocking=True)
                     y = hy[k][:b].to(self.device, non_blocking=True)
+                    if p is not None:
+                        p.device_buf = hp[k][:p.packed_nbytes(b)].to(self.device,
+                                                                     non_blocking=True)
+                        # the raw batch and the tables are allocated and used on the copy
+                        # stream alone: dropping them here is stream-ordered
+                        x = aug.apply_device(x, p)
+                        p.device_buf = None
                     ev = torch.cuda.Event()
                     ev.record(copy_stream)
                 inflight.append((k, ev))
             else:
-                x, y, ev = hx[k][:b].clone(), hy[k][:b].clone(), None
+                if p is not None:
+                    x = torch.from_numpy(aug.apply_host_batch(hx[k].numpy()[:b], p))
+                    y, ev = hy[k][:b].clone(), None
+                else:
+                    x, y, ev = hx[k][:b].clone(), hy[k][:b].clone(), None
                 free.put(k)
             pending.append((x, y, idx, ev))
 
