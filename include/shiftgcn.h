@@ -23,9 +23,10 @@ extern "C" {
 
 #define SGCN_EINVAL (-22)
 #define SGCN_ABI_VERSION 25
-/* Set in sgcn_abi_version()'s value by a diagnostic build (SGCN_PW_DIAG, SGCN_PW_STAMPS,
- * SGCN_DIAG_*: timing probes whose results are WRONG, `make diag` only); the Python loader
- * refuses such a library. */
+/* Set in sgcn_abi_version()'s value by a diagnostic build (SGCN_PW_DIAG, SGCN_PW_STAMPS:
+ * timing probes whose results are WRONG, `make diag` only); the Python loader refuses such
+ * a library. The SGCN_DIAG_* bound probes are retired (DESIGN.md, row "diagnostics out of
+ * the product"); `make` still refuses the prefix. */
 #define SGCN_ABI_DIAG_FLAG 0x10000
 
 /* ABI version of the loaded library (== SGCN_ABI_VERSION). 19: the measured-and-rejected
@@ -243,7 +244,7 @@ int sgcn_pw_fwd_bf16(const float* w, int w_mcontig, const float* bias, const flo
  * EVERY channel's xpos lies in (-2^-25, 0], two taps of the element's own column, rows
  * floor(y) and floor(y)+1 (there the .cu:73 blend reduces to q21*(1-dy) + q22*dy exactly:
  * bit-identical still); 2 = also when channels have 0 < xpos < 2^-25 (1 - dx rounds to 1;
- * the dropped dx terms weigh < 2^-25: within 3e-8 * max|tap| of sgcn_tshift_fwd). A launch
+ * the dropped dx terms weigh < 2^-25: within 2e-7 * max|tap| of sgcn_tshift_fwd). A launch
  * with any other channel uses four taps for all (decided on the device, per launch). */
 size_t sgcn_pw_tshift_ws_bytes(int K);
 int sgcn_pw_fwd_tshift(const float* w, const float* bias, const float* x, long long x_bstride,

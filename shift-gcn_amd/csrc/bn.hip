@@ -887,9 +887,6 @@ __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
     float2* __restrict__ bn_part, int C, int T, int V, const float* __restrict__ add2m,
     int flags) {
   SGCN_CRIT_PRIO();
-#ifdef SGCN_DIAG_F1B_REAL
-  return;   // timing diagnostic only: the pass is fused into the contraction (pwconv.hip)
-#endif
   __shared__ float s0[NT];
   __shared__ float red[2 * NT / 64];
   const int plane = blockIdx.x, c = plane % C, rc = c % V;
@@ -908,14 +905,7 @@ __global__ __launch_bounds__(NT) void gcn_dx_finish_ja_kernel(
   float gv[LPT], xq[LPT], a1[ADD1 ? LPT : 1], a2[ADD2 && !A2P ? LPT : 1], a2q[A2M ? LPT : 1];
   float sv[PART ? LPT : 1];
   {
-#ifdef SGCN_DIAG_F1B_BOUND
-    // timing diagnostic only (results wrong): dXt is never read (range 0), with the gcn dX
-    // contraction's stores dropped (pwconv.hip): the bound of fusing this pass into that
-    // contraction's epilogue (verdict r05, next #5)
-    const auto gr = make_rsrc(dxt + off, 0u), xr = make_rsrc(x0 + off, pb);
-#else
     const auto gr = make_rsrc(dxt + off, pb), xr = make_rsrc(x0 + off, pb);
-#endif
 #pragma unroll
     for (int e = 0; e < LPT; ++e) {
       gv[e] = bload(gr, uo + e * vstep, 0);

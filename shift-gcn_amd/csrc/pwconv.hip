@@ -90,9 +90,6 @@ struct FwdArgs {
   // extent loads 0 / drops the store) and epilogue flags
   unsigned x_bytes, y_bytes, a_bytes, mask_bytes;
   int relu;
-#ifdef SGCN_DIAG_F1B_REAL
-  int diag_f1b;
-#endif
 };
 
 // the FastDiv constants of a.T * a.V and a.V (every FwdArgs launch sets them)
@@ -192,14 +189,16 @@ __device__ __forceinline__ int rot_step(int d, int rsign, int V) { return pmod(d
 // For x = xpos in (-2^-25, 0): x1 = -1 and dx = x + 1 rounds to exactly 1.0f, so 1-dx = 0,
 // q11 and q12 only add zeros and q21*dx = q21, q22*dx = q22: the value IS
 // q21*(1-dy) + q22*dy with q21, q22 on the element's own column. For x = 0: x1 = 0, dx = 0,
-// and it is q11*(1-dy) + q12*dy, the same two taps. Those channels (every channel of a
-// model whose xpos was initialised in U(-1e-8, 0], shift.py:39: its gradient is exactly
-// +-0, .cu:386, so only weight decay moves it, towards 0) need two taps of one column
+// and it is q11*(1-dy) + q12*dy, the same two taps. Those channels (about half of a freshly
+// initialised model's: xpos starts in U(-1e-8, 1e-8), model/Temporal_shift/cuda/shift.py:42,
+// and its gradient is exactly +-0, .cu:386, so only weight decay moves it, towards 0; the
+// positive half takes mode 2, below) need two taps of one column
 // instead of four: half the bytes returned into VGPRs and a third of the VALU, which on
 // gfx950 is what the fused operand costs against the fp32 MFMA (profiles/r05_dma2/).
 // Bit-identical to the four-tap form (up to the sign of an exact zero). With mode 2 the
 // channels with 0 < x < 2^-25 (1-dx rounds to 1) take it too, dropping the q21*dx and
-// q22*dx terms (|dx| < 3e-8: within 3e-8 * max|q| of the exact value, north_star's 1e-5).
+// q22*dx terms (|dx| < 2^-25; tested within 2e-7 * max|q| of the exact value, north_star's
+// 1e-5).
 // The choice is per launch: the table kernel also writes one flag, set when EVERY channel
 // qualifies, which the contraction reads once at its start (a per-row choice costs a
 // scalar-load wait per operand row inside the main loop: measured 2x slower); a launch with
@@ -280,7 +279,156 @@ __global__ __launch_bounds__(256) void tshift_two_row_flag_kernel(int K,
 // from per-element selects. Only the joint-shift rotation (XROT) and the feature mask
 // cost VALU per loaded element.
 // ------------------------------------------------------------------------------------
-//
+
+// A thread's position column of a forward tile (fixed for the tile).
+struct TileCol {
+  unsigned xcol;   // byte offset of (sample, t[, v]) in X; p.x_bytes past P (loads return 0)
+  int vv, tt;      // joint and frame
+  bool ok;         // the column is a position (p0 + nb < P)
+};
+
+// Tile-column setup of the forward kernels, tile at (m0, p0): fills bias_s / rot_s (per tile
+// row: bias, shift_out rotation) and ycol_s / v_s (per tile column: byte offset of (b, t) in
+// Y, p.y_bytes past P so that stores are dropped; joint v) and returns thread tid's column
+// nb = tid % BN. XNOV: xcol without v (the rotated operand adds its own joint per row).
+template <int BM, int BN, int NT, bool XNOV>
+__device__ __forceinline__ TileCol tile_columns(const FwdArgs& p, int p0, int m0, float* bias_s,
+                                                int* rot_s, unsigned* ycol_s, int* v_s) {
+  const int tid = threadIdx.x, nb = tid % BN;
+  const int V = p.V, N = p.T * V, M = p.M;
+  const int P = p.B * N;                 // < 2^31 (host-checked)
+  for (int i = tid; i < BM; i += NT) {
+    bias_s[i] = (p.bias && m0 + i < M) ? p.bias[m0 + i] : 0.f;
+    rot_s[i] = p.y.rsign ? pmod(p.y.rsign * (m0 + i), V) : 0;
+  }
+  const int pc = p0 + nb;
+  TileCol c{p.x_bytes, 0, 0, pc < P};
+  unsigned ycol = p.y_bytes;
+  if (pc < P) {
+    const int b = fdiv(pc, p.divN_m, p.divN_s);
+    const int n = pc - b * N;
+    const int t = fdiv(n, p.divV_m, p.divV_s);
+    c.tt = t;
+    c.vv = n - t * V;
+    // 32-bit offsets: every term is at most the operand's byte extent (< 2^32, host-checked)
+    c.xcol = ((unsigned)b * (unsigned)p.x.bstride + (unsigned)t * (unsigned)(p.x.tstride * V) +
+              (unsigned)(XNOV ? 0 : c.vv)) * 4u;
+    ycol = ((unsigned)b * (unsigned)p.y.bstride + (unsigned)t * (unsigned)(p.y.tstride * V)) * 4u;
+  }
+  if (tid < BN) {
+    ycol_s[nb] = ycol;
+    v_s[nb] = c.vv;
+  }
+  return c;
+}
+
+// Tile store of the forward kernels: Y (+)= act(acc + bias) for the BM x BN tile at row m0
+// whose columns tile_columns described. The MFMA C/D map (col = lane&31, row = (r&3) +
+// 8*(r>>2) + 4*(lane>>5); the same for every operand type of the 32 x 32 forms) leaves each
+// wave holding 32-column pieces of 64 rows; stored straight from registers, a 128-B line of
+// a Y row is completed by several waves (and tiles) at different times, and lines evicted
+// from L2 half-written cost a second partial write (PMC: 1.20x the algorithmic bytes at
+// M >= 128). So the tile is staged through LDS (smem: WM*16 x BN floats, the operand
+// stages' memory, which every wave has finished reading) in passes of 16 rows per wave
+// band, and each wave then stores whole tile rows: 64 lanes on 64 consecutive positions,
+// BN/64 instructions per row, every line completed at once.
+template <int BM, int BN, int WM, int WN, bool ACCUM, typename SF>
+__device__ __forceinline__ void store_tile(const FwdArgs& p,
+                                           const f32x16 (&acc)[BM / WM / 32][BN / WN / 32],
+                                           SF* smem, const float* bias_s, const int* rot_s,
+                                           const unsigned* ycol_s, const int* v_s, int m0,
+                                           int wid, int wm, int wn, int lane) {
+  constexpr int MI = BM / WM / 32, NJ = BN / WN / 32;
+  constexpr int NW = WM * WN;
+  constexpr int RB = WM * 16;      // staged rows per pass
+  constexpr int CQ = BN / 64;      // 64-column groups per row
+  constexpr int RPW = RB / NW;     // rows per wave per pass
+  static_assert(BN % 64 == 0 && RB % NW == 0, "epilogue staging");
+  const int V = p.V, M = p.M;
+  const int kl = lane >> 5, cl = lane & 31;
+  const auto yr = make_rsrc(p.y.ptr, p.y_bytes);
+  const unsigned ycs4 = (unsigned)(p.y.cstride * 4);
+  unsigned ycolq[CQ];
+  int vq[CQ];
+#pragma unroll
+  for (int q = 0; q < CQ; ++q) {
+    ycolq[q] = ycol_s[lane + 64 * q];
+    vq[q] = v_s[lane + 64 * q];
+  }
+  // ACCUM: the old value of an output element is loaded for all of this wave's rows of a
+  // pass BEFORE the pass's LDS staging: in the store loop it would wait a memory round trip
+  // (a load after the previous row's stores)
+  float pf[ACCUM ? RPW : 1][ACCUM ? CQ : 1];
+  auto row_of = [&](int i, int h, int k) {   // tile row of this wave's k-th row of a pass
+    const int lr = wid + k * NW;
+    return (lr >> 4) * (BM / WM) + i * 32 + 16 * h + (lr & 15);   // uniform
+  };
+  // (ROT a compile-time branch: without the shift_out rotation a lane's store offsets are
+  // the same for every row, hoisted out of the row loops — the epilogue is most of the
+  // VALU work of a K <= 128 tile, which shares the issue with the fp32 MFMA)
+  auto epilogue = [&](auto relu_tag, auto rot_tag) {
+    constexpr bool RELU = decltype(relu_tag)::value;
+    constexpr bool ROT = decltype(rot_tag)::value;
+    auto voff_of = [&](int trow, int q) {
+      int vo = vq[q];
+      if constexpr (ROT) {   // shift_out rotation of the stored joint
+        vo += rot_s[trow];
+        vo = vo >= V ? vo - V : vo;
+      }
+      return vo;
+    };
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if constexpr (ACCUM) {
+#pragma unroll
+          for (int k = 0; k < RPW; ++k) {
+            const int trow = row_of(i, h, k);
+            // a row past M: every address past its extent (loads 0, nothing stored later)
+            const unsigned soff = m0 + trow < M ? (unsigned)(m0 + trow) * ycs4 : p.y_bytes;
+#pragma unroll
+            for (int q = 0; q < CQ; ++q)
+              pf[k][q] = bload(yr, ycolq[q] + (unsigned)(voff_of(trow, q) * 4), soff);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int rr = 0; rr < 8; ++rr) {
+            const int r = 8 * h + rr;
+            const int lr = wm * 16 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * kl;
+            smem[lr * BN + wn * (BN / WN) + j * 32 + cl] = acc[i][j][r];
+          }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < RPW; ++k) {
+          const int lr = wid + k * NW;
+          const int trow = row_of(i, h, k);
+          if (m0 + trow >= M) break;   // rows past M (they increase with k)
+          const float bv = bias_s[trow];
+          const unsigned soff = (unsigned)(m0 + trow) * ycs4;
+#pragma unroll
+          for (int q = 0; q < CQ; ++q) {
+            const unsigned voff = ycolq[q] + (unsigned)(voff_of(trow, q) * 4);
+            float val = smem[lr * BN + lane + 64 * q] + bv;
+            if (RELU) val = fmaxf(val, 0.f);
+            if constexpr (ACCUM) val += pf[k][q];
+            bstore(yr, val, voff, soff);
+          }
+        }
+        __syncthreads();
+      }
+  };
+  if (p.y.rsign != 0) {
+    if (p.relu) epilogue(std::true_type{}, std::true_type{});
+    else epilogue(std::false_type{}, std::true_type{});
+  } else {
+    if (p.relu) epilogue(std::true_type{}, std::false_type{});
+    else epilogue(std::false_type{}, std::false_type{});
+  }
+}
+
 // AR (K <= 64, the HBM-bound 64-row tiles): the whole A (K x BM) is staged into LDS once in
 // the prologue and B is single-buffered (a second barrier per stage): 35 instead of 43 KB of
 // LDS, so four workgroups fit a CU instead of three — a third more operand bytes in flight.
@@ -316,8 +464,7 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid - (wid / WN) * WN;
-  const int V = p.V, N = p.T * V, K = p.K, M = p.M;
-  const int P = p.B * N;                 // < 2^31 (host-checked)
+  const int V = p.V, K = p.K, M = p.M;
   const int p0 = xcd_tile<SGCN_PW_XCD>(blockIdx.x, gridDim.x) * BN;
   const int m0 = blockIdx.y * BM;
   const auto xr = make_rsrc(p.x.ptr, p.x_bytes);
@@ -328,36 +475,13 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
   const bool two =
       TSH && ((const __attribute__((address_space(4))) int*)p.ts)[K * kTsWords] != 0;
 
-  for (int i = tid; i < BM; i += NT) {
-    bias_s[i] = (p.bias && m0 + i < M) ? p.bias[m0 + i] : 0.f;
-    rot_s[i] = p.y.rsign ? pmod(p.y.rsign * (m0 + i), V) : 0;
-  }
-
   // ---- B column of this thread (fixed for the tile) ----
+  const TileCol col = tile_columns<BM, BN, NT, XROT>(p, p0, m0, bias_s, rot_s, ycol_s, v_s);
   const int nb = tid % BN;
   const int kb0 = __builtin_amdgcn_readfirstlane(tid / BN);
-  int vv = 0, tt = 0;
-  unsigned xcol = p.x_bytes;   // out of range: loads return 0
-  const bool colok = p0 + nb < P;
-  {
-    const int pc = p0 + nb;
-    unsigned ycol = p.y_bytes;   // out of range: stores dropped
-    if (pc < P) {
-      const int b = fdiv(pc, p.divN_m, p.divN_s);
-      const int n = pc - b * N;
-      const int t = fdiv(n, p.divV_m, p.divV_s);
-      tt = t;
-      vv = n - t * V;
-      // 32-bit offsets: every term is at most the operand's byte extent (< 2^32, host-checked)
-      xcol = ((unsigned)b * (unsigned)p.x.bstride + (unsigned)t * (unsigned)(p.x.tstride * V) +
-              (unsigned)(XROT ? 0 : vv)) * 4u;
-      ycol = ((unsigned)b * (unsigned)p.y.bstride + (unsigned)t * (unsigned)(p.y.tstride * V)) * 4u;
-    }
-    if (tid < BN) {
-      ycol_s[nb] = ycol;
-      v_s[nb] = vv;
-    }
-  }
+  const unsigned xcol = col.xcol;
+  const int vv = col.vv, tt = col.tt;
+  const bool colok = col.ok;
   const unsigned xcs4 = (unsigned)(p.x.cstride * 4);
   const int bstep = XROT ? rot_step(KSTEP_B, p.x.rsign, V) : 0;
   const int kstage_rot = XROT ? rot_step(BK, p.x.rsign, V) : 0;
@@ -574,120 +698,10 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
   }
 
   SGCN_PW_STAMP(2);
-  // ---- epilogue. The MFMA C/D map (col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5))
-  // leaves each wave holding 32-column pieces of 64 rows; stored straight from registers,
-  // a 128-B line of a Y row is completed by several waves (and tiles) at different times,
-  // and lines evicted from L2 half-written cost a second partial write (PMC: 1.20x the
-  // algorithmic bytes at M >= 128). So the tile is staged through LDS in passes of 16
-  // rows per wave band, and each wave then stores whole tile rows: 64 lanes on 64
-  // consecutive positions, BN/64 instructions per row, every line completed at once.
-  const auto yr = make_rsrc(p.y.ptr, p.y_bytes);
-  const unsigned ycs4 = (unsigned)(p.y.cstride * 4);
-  constexpr int NW = WM * WN;
-  constexpr int RB = WM * 16;      // staged rows per pass
-  constexpr int CQ = BN / 64;      // 64-column groups per row
-  static_assert(BN % 64 == 0 && RB * BN <= ASZ + BSZ, "epilogue staging");
-  unsigned ycolq[CQ];
-  int vq[CQ];
-#pragma unroll
-  for (int q = 0; q < CQ; ++q) {
-    ycolq[q] = ycol_s[lane + 64 * q];
-    vq[q] = v_s[lane + 64 * q];
-  }
-  const bool rotated = p.y.rsign != 0;
-  constexpr int RPW = RB / NW;     // rows per wave per pass
-  static_assert(RB % NW == 0, "rows per wave");
-  // the global load an output element needs besides the accumulator (ACCUM: the old
-  // value) is issued for all of this wave's rows of a pass BEFORE the pass's LDS staging: in
-  // the store loop it would wait a memory round trip (a load after the previous row's stores)
-#ifdef SGCN_DIAG_F1B_REAL
-  // timing diagnostic only (results wrong): the gcn input-gradient contraction's epilogue
-  // also reads three more tensors per element (what gcn_dx_finish's work would read there:
-  // x0, the residual gradient and its mask / the previous BatchNorm's input), see sgcn_pw_fwd
-  constexpr int NPF = ACCUM ? 4 : 0;
-  const int npf = p.diag_f1b ? 4 : 1;
-#else
-  constexpr int NPF = ACCUM ? 1 : 0;
-  constexpr int npf = 1;
-#endif
-  float pf[NPF ? RPW : 1][NPF ? CQ : 1][NPF ? NPF : 1];
-  auto row_of = [&](int i, int h, int k) {   // (tile row, its store row offset)
-    const int lr = wid + k * NW;
-    return (lr >> 4) * (BM / WM) + i * 32 + 16 * h + (lr & 15);   // uniform
-  };
-  // (ROT a compile-time branch: without the shift_out rotation a lane's store offsets are
-  // the same for every row, hoisted out of the row loops — the epilogue is most of the
-  // VALU work of a K <= 128 tile, which shares the issue with the fp32 MFMA)
-  auto epilogue = [&](auto relu_tag, auto rot_tag) {
-    constexpr bool RELU = decltype(relu_tag)::value;
-    constexpr bool ROT = decltype(rot_tag)::value;
-    auto voff_of = [&](int trow, int q) {
-      int vo = vq[q];
-      if constexpr (ROT) {   // shift_out rotation of the stored joint
-        vo += rot_s[trow];
-        vo = vo >= V ? vo - V : vo;
-      }
-      return vo;
-    };
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        if (NPF) {
-#pragma unroll
-          for (int k = 0; k < RPW; ++k) {
-            const int trow = row_of(i, h, k);
-            // a row past M: every address past its extent (loads 0, nothing stored later)
-            const unsigned soff = m0 + trow < M ? (unsigned)(m0 + trow) * ycs4 : p.y_bytes;
-#pragma unroll
-            for (int q = 0; q < CQ; ++q) {
-              const int vo = voff_of(trow, q);
-              const unsigned voff = ycolq[q] + (unsigned)(vo * 4);
-              pf[k][q][0] = bload(yr, voff, soff);
-#pragma unroll
-              for (int j = 1; j < NPF; ++j)   // (diagnostic: other rows of Y, in range)
-                pf[k][q][j] = j < npf ? bload(yr, voff, (unsigned)((m0 + trow + j) % M) * ycs4)
-                                      : 0.f;
-            }
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int rr = 0; rr < 8; ++rr) {
-            const int r = 8 * h + rr;
-            const int lr = wm * 16 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * kl;
-            smem[lr * BN + wn * (BN / WN) + j * 32 + cl] = acc[i][j][r];
-          }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-          const int lr = wid + k * NW;
-          const int trow = row_of(i, h, k);
-          if (m0 + trow >= M) break;   // rows past M (they increase with k)
-          const float bv = bias_s[trow];
-          const unsigned soff = (unsigned)(m0 + trow) * ycs4;
-#pragma unroll
-          for (int q = 0; q < CQ; ++q) {
-            const unsigned voff = ycolq[q] + (unsigned)(voff_of(trow, q) * 4);
-            float val = smem[lr * BN + lane + 64 * q] + bv;
-            if (RELU) val = fmaxf(val, 0.f);
-            if constexpr (ACCUM) val += pf[k][q][0];
-#pragma unroll
-            for (int j = 1; j < NPF; ++j) val += pf[k][q][j];
-            bstore(yr, val, voff, soff);
-          }
-        }
-        __syncthreads();
-      }
-  };
-  if (rotated) {
-    if (p.relu) epilogue(std::true_type{}, std::true_type{});
-    else epilogue(std::false_type{}, std::true_type{});
-  } else {
-    if (p.relu) epilogue(std::true_type{}, std::false_type{});
-    else epilogue(std::false_type{}, std::false_type{});
-  }
+  // ---- epilogue: the operand stages' memory now stages the accumulator tile ----
+  static_assert(WM * 16 * BN <= ASZ + BSZ, "epilogue staging");
+  store_tile<BM, BN, WM, WN, ACCUM>(p, acc, smem, bias_s, rot_s, ycol_s, v_s, m0, wid, wm, wn,
+                                    lane);
 #ifdef SGCN_PW_STAMPS
   __builtin_amdgcn_s_waitcnt(0);   // stores issued and drained
 #endif
@@ -712,9 +726,9 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_kernel(FwdArgs p) {
 //  * A, m-contiguous (Linear_weight): as X, a thread owns a row m and eight k.
 // Rows k >= K are out of the descriptor range for BOTH operands (zeros in LDS; a k past K
 // is never read from memory), rows m >= M and columns past P likewise. Two stages are
-// double-buffered with one barrier each; the epilogue is pwg_fwd_kernel's (the C/D map of
-// the 32 x 32 forms does not depend on the operand type), copied so that the fp32
-// kernels' code stays what it was.
+// double-buffered with one barrier each; tile-column setup and tile store are the ones
+// pwg_fwd_kernel calls (tile_columns, store_tile: the C/D map of the 32 x 32 forms does not
+// depend on the operand type).
 // Not pinned: subnormal, infinite and NaN operands.
 // ------------------------------------------------------------------------------------
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -741,12 +755,8 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_bf16_kernel(FwdArgs p) {
   static_assert(MI >= 1 && NJ >= 1 && BK == 32, "bad tile");
   static_assert(NT % BN == 0 && KG % BGS == 0 && B_IT >= 1, "bad tile (X staging)");
   static_assert(BM % A_ROWS == 0 && NT % BM == 0 && BM % 64 == 0, "bad tile (A staging)");
-  constexpr int NW = WM * WN;
-  constexpr int RB = WM * 16;      // epilogue: staged rows per pass
-  constexpr int CQ = BN / 64;      // 64-column groups per row
-  constexpr int RPW = RB / NW;     // rows per wave per pass
-  static_assert(BN % 64 == 0 && RB % NW == 0, "epilogue staging");
-  constexpr int OPS = 2 * (ASZ + BSZ), EPS = RB * BN / 4;
+  // slots of the operand stages and of store_tile's staged rows (WM * 16 x BN floats)
+  constexpr int OPS = 2 * (ASZ + BSZ), EPS = WM * 16 * BN / 4;
   __shared__ lds_slot smem[OPS > EPS ? OPS : EPS];
   lds_slot* const As = smem;                   // [2][KG][AG]
   lds_slot* const Bs = smem + 2 * ASZ;         // [2][KG][BG]
@@ -758,41 +768,17 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_bf16_kernel(FwdArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid - (wid / WN) * WN;
-  const int V = p.V, N = p.T * V, K = p.K, M = p.M;
-  const int P = p.B * N;                 // < 2^31 (host-checked)
+  const int K = p.K, M = p.M;
   const int p0 = xcd_tile<SGCN_PW_XCD>(blockIdx.x, gridDim.x) * BN;
   const int m0 = blockIdx.y * BM;
   const auto xr = make_rsrc(p.x.ptr, p.x_bytes);
   const auto ar = make_rsrc(p.A, p.a_bytes);
 
-  for (int i = tid; i < BM; i += NT) {
-    bias_s[i] = (p.bias && m0 + i < M) ? p.bias[m0 + i] : 0.f;
-    rot_s[i] = p.y.rsign ? pmod(p.y.rsign * (m0 + i), V) : 0;
-  }
-
   // ---- X column of this thread (fixed for the tile) ----
+  const unsigned xcol =
+      tile_columns<BM, BN, NT, false>(p, p0, m0, bias_s, rot_s, ycol_s, v_s).xcol;
   const int nb = tid % BN;
   const int bg0 = __builtin_amdgcn_readfirstlane(tid / BN);
-  unsigned xcol = p.x_bytes;   // out of range: loads return 0
-  {
-    const int pc = p0 + nb;
-    unsigned ycol = p.y_bytes;   // out of range: stores dropped
-    int vv = 0;
-    if (pc < P) {
-      const int b = fdiv(pc, p.divN_m, p.divN_s);
-      const int n = pc - b * N;
-      const int t = fdiv(n, p.divV_m, p.divV_s);
-      vv = n - t * V;
-      // 32-bit offsets: every term is at most the operand's byte extent (< 2^32, host-checked)
-      xcol = ((unsigned)b * (unsigned)p.x.bstride + (unsigned)t * (unsigned)(p.x.tstride * V) +
-              (unsigned)vv) * 4u;
-      ycol = ((unsigned)b * (unsigned)p.y.bstride + (unsigned)t * (unsigned)(p.y.tstride * V)) * 4u;
-    }
-    if (tid < BN) {
-      ycol_s[nb] = ycol;
-      v_s[nb] = vv;
-    }
-  }
   const unsigned xcs4 = (unsigned)(p.x.cstride * 4);
 
   // ---- A elements of this thread ----
@@ -902,72 +888,9 @@ __global__ __launch_bounds__(64 * WM * WN) void pwg_fwd_bf16_kernel(FwdArgs p) {
     __syncthreads();
   }
 
-  // ---- epilogue (pwg_fwd_kernel's: the tile staged through LDS in passes of 16 rows per
-  // wave band, each wave then stores whole tile rows, every 128-B line completed at once) ----
-  lds_float* const smemf = reinterpret_cast<lds_float*>(smem);
-  const auto yr = make_rsrc(p.y.ptr, p.y_bytes);
-  const unsigned ycs4 = (unsigned)(p.y.cstride * 4);
-  unsigned ycolq[CQ];
-  int vq[CQ];
-#pragma unroll
-  for (int q = 0; q < CQ; ++q) {
-    ycolq[q] = ycol_s[lane + 64 * q];
-    vq[q] = v_s[lane + 64 * q];
-  }
-  const bool rotated = p.y.rsign != 0;
-  auto row_of = [&](int i, int h, int k) {   // tile row of this wave's k-th row of a pass
-    const int lr = wid + k * NW;
-    return (lr >> 4) * (BM / WM) + i * 32 + 16 * h + (lr & 15);   // uniform
-  };
-  auto epilogue = [&](auto relu_tag, auto rot_tag) {
-    constexpr bool RELU = decltype(relu_tag)::value;
-    constexpr bool ROT = decltype(rot_tag)::value;
-    auto voff_of = [&](int trow, int q) {
-      int vo = vq[q];
-      if constexpr (ROT) {   // shift_out rotation of the stored joint
-        vo += rot_s[trow];
-        vo = vo >= V ? vo - V : vo;
-      }
-      return vo;
-    };
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-          for (int rr = 0; rr < 8; ++rr) {
-            const int r = 8 * h + rr;
-            const int lr = wm * 16 + (r & 3) + 8 * ((r >> 2) & 1) + 4 * kl;
-            smemf[lr * BN + wn * (BN / WN) + j * 32 + cl] = acc[i][j][r];
-          }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < RPW; ++k) {
-          const int lr = wid + k * NW;
-          const int trow = row_of(i, h, k);
-          if (m0 + trow >= M) break;   // rows past M (they increase with k)
-          const float bv = bias_s[trow];
-          const unsigned soff = (unsigned)(m0 + trow) * ycs4;
-#pragma unroll
-          for (int q = 0; q < CQ; ++q) {
-            const unsigned voff = ycolq[q] + (unsigned)(voff_of(trow, q) * 4);
-            float val = smemf[lr * BN + lane + 64 * q] + bv;
-            if (RELU) val = fmaxf(val, 0.f);
-            bstore(yr, val, voff, soff);
-          }
-        }
-        __syncthreads();
-      }
-  };
-  if (rotated) {
-    if (p.relu) epilogue(std::true_type{}, std::true_type{});
-    else epilogue(std::false_type{}, std::true_type{});
-  } else {
-    if (p.relu) epilogue(std::true_type{}, std::false_type{});
-    else epilogue(std::false_type{}, std::false_type{});
-  }
+  // ---- epilogue: the operand stages' memory now stages the accumulator tile ----
+  store_tile<BM, BN, WM, WN, false>(p, acc, reinterpret_cast<lds_float*>(smem), bias_s, rot_s,
+                                    ycol_s, v_s, m0, wid, wm, wn, lane);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1578,9 +1501,9 @@ __global__ __launch_bounds__(256) void pw_fwd_smallm_kernel(FwdArgs p) {
 // ------------------------------------------------------------------------------------
 // launch helpers (pw_forms.hpp chooses the family, tile and split geometry)
 // ------------------------------------------------------------------------------------
-inline dim3 pwg_grid(const FwdArgs& a, const PwFwdTile& t) {
+inline dim3 pwg_grid(const FwdArgs& a, int bm, int bn) {
   const long long P = (long long)a.B * a.T * a.V;   // < 2^31 (checked by the caller)
-  return dim3((unsigned)cdiv(P, t.bn), (unsigned)cdiv(a.M, t.bm));
+  return dim3((unsigned)cdiv(P, bn), (unsigned)cdiv(a.M, bm));
 }
 
 // pwg_fwd_kernel on a tile of kPwFwdTiles (false: another tile, nothing launched)
@@ -1588,7 +1511,7 @@ bool launch_pwg(const FwdArgs& a, const PwFwdTile& t, bool accum, hipStream_t st
   return with_form<kPwFwdTiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AR, auto MASK,
                                        auto XROT, auto AMC, auto ACCUM) {
     pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, AMC, ACCUM, false, AR>
-        <<<pwg_grid(a, t), 64 * WM * WN, 0, st>>>(a);
+        <<<pwg_grid(a, BM, BN), 64 * WM * WN, 0, st>>>(a);
   }, a.mask != nullptr, a.x.rsign != 0, a.a_mcontig != 0, accum);
 }
 
@@ -1596,16 +1519,14 @@ bool launch_pwg(const FwdArgs& a, const PwFwdTile& t, bool accum, hipStream_t st
 bool launch_pwg_tsh(const FwdArgs& a, const PwFwdTile& t, hipStream_t st) {
   return with_form<kPwTshTiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AR) {
     pwg_fwd_kernel<BM, BN, WM, WN, false, false, false, false, true, AR>
-        <<<pwg_grid(a, t), 64 * WM * WN, 0, st>>>(a);
+        <<<pwg_grid(a, BM, BN), 64 * WM * WN, 0, st>>>(a);
   });
 }
 
 // pwg_fwd_bf16_kernel on a tile of kPwBf16Tiles
 bool launch_pwg_bf16(const FwdArgs& a, const PwBf16Tile& t, hipStream_t st) {
-  const long long P = (long long)a.B * a.T * a.V;   // < 2^31 (checked by the caller)
-  const dim3 grid((unsigned)cdiv(P, t.bn), (unsigned)cdiv(a.M, t.bm));
   return with_form<kPwBf16Tiles>(t, [&](auto BM, auto BN, auto WM, auto WN, auto AMC) {
-    pwg_fwd_bf16_kernel<BM, BN, WM, WN, AMC><<<grid, 64 * WM * WN, 0, st>>>(a);
+    pwg_fwd_bf16_kernel<BM, BN, WM, WN, AMC><<<pwg_grid(a, BM, BN), 64 * WM * WN, 0, st>>>(a);
   }, a.a_mcontig != 0);
 }
 
@@ -1642,7 +1563,18 @@ unsigned plane_bytes(long long bstride, long long cstride, int tstride, int B, i
   return (unsigned)(e * 4);
 }
 
-// what both forward entry points pass: weights (k- or m-contiguous), planes, sizes, divisors
+// what every forward entry point requires of its sizes and its two planes (false: EINVAL):
+// positions and per-operand offsets index in 32 bits, extents fit the buffer ranges
+bool fwd_shape_ok(int B, int M, int K, int T, int V, const Plane& x, const OutPlane& y) {
+  return B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768 &&
+         x.tstride >= 1 && y.tstride >= 1 && x.rsign >= -1 && x.rsign <= 1 &&
+         y.rsign >= -1 && y.rsign <= 1 && x.cstride * (long long)K < (1LL << 31) &&
+         y.cstride * (long long)M < (1LL << 31) && (long long)B * T * V < (1LL << 31) &&
+         pw_extent(x.bstride, x.cstride, x.tstride, B, K, T, V) < kPwMaxElems &&
+         pw_extent(y.bstride, y.cstride, y.tstride, B, M, T, V) < kPwMaxElems;
+}
+
+// what every forward entry point passes: weights (k- or m-contiguous), planes, sizes, divisors
 // and byte ranges; every optional pointer (mask, ts, xs) starts null
 FwdArgs fwd_args(const float* w, int w_mcontig, const float* bias, const Plane& x,
                  const OutPlane& y, int relu, int B, int M, int K, int T, int V) {
@@ -1678,52 +1610,17 @@ int sgcn_pw_fwd(const float* w, int w_mcontig, const float* bias, const float* x
                 const float* mask, float* y, long long y_bstride, long long y_cstride,
                 int y_tstride, int y_rsign, int relu, int accumulate, int B, int M, int K,
                 int T, int V, void* stream) {
-  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
-  SGCN_REQUIRE(x_tstride >= 1 && y_tstride >= 1);
-  SGCN_REQUIRE(x_rsign >= -1 && x_rsign <= 1 && y_rsign >= -1 && y_rsign <= 1);
-  SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
+  const Plane xp{x, x_bstride, x_cstride, x_tstride, x_rsign};
+  const OutPlane yp{y, y_bstride, y_cstride, y_tstride, y_rsign};
+  SGCN_REQUIRE(fwd_shape_ok(B, M, K, T, V, xp, yp));
   SGCN_REQUIRE(!mask || V <= kMaskMaxV);
-  SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
-  // operand extents must fit the 32-bit buffer ranges
-  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, x_tstride, B, K, T, V) < kPwMaxElems);
-  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, y_tstride, B, M, T, V) < kPwMaxElems);
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(w && x && y);
-  FwdArgs a = fwd_args(w, w_mcontig, bias, {x, x_bstride, x_cstride, x_tstride, x_rsign},
-                       {y, y_bstride, y_cstride, y_tstride, y_rsign}, relu, B, M, K, T, V);
+  FwdArgs a = fwd_args(w, w_mcontig, bias, xp, yp, relu, B, M, K, T, V);
   a.mask = mask;
   a.mask_bytes = mask ? (unsigned)(V * K * 4) : 0u;
   hipStream_t st = (hipStream_t)stream;
-  bool ac = accumulate != 0;
-#ifdef SGCN_DIAG_X1B_BOUND
-  // timing diagnostic only (results wrong): temporal_linear's input-gradient contraction
-  // (W^T read m-contiguous, no bias / relu / accumulate) at M >= SGCN_DIAG_X1B_BOUND stores
-  // nothing, i.e. the dAs write a fused shift_in backward epilogue would never make
-  if (w_mcontig && !bias && !relu && !ac && M >= SGCN_DIAG_X1B_BOUND) a.y_bytes = 0;
-#endif
-#ifdef SGCN_DIAG_F1B_REAL
-  // timing diagnostic only (results wrong): the gcn input-gradient contraction (see
-  // SGCN_DIAG_F1B_BOUND) as an accumulating launch whose epilogue reads four tensors'
-  // worth per element (the finish pass's x0 / residual-gradient / mask / BatchNorm-input
-  // reads moved into the epilogue) while gcn_dx_finish does nothing: the realistic cost of
-  // fusing that pass into this contraction (the bound alone drops the work)
-  if (!w_mcontig && !bias && !relu && !ac && M > kSmallM) {
-    a.diag_f1b = 1;
-    ac = true;
-  }
-#endif
-#ifdef SGCN_DIAG_F1B_BOUND
-  // timing diagnostic only (results wrong): the Shift_gcn input-gradient contraction
-  // (Linear_weight read k-contiguous as W^T, no bias / relu / accumulate) stores nothing,
-  // and gcn_dx_finish reads no dXt (bn.hip): the whole dXt round trip free
-  if (!w_mcontig && !bias && !relu && !ac) a.y_bytes = 0;
-#endif
-#ifdef SGCN_DIAG_F2_BOUND
-  // timing diagnostic only (tools/ab_variant.sh; results are wrong): the stride-2 residual
-  // conv's read of the unit input is dropped by the range check, i.e. the most any fusion
-  // sharing that read with the `down` conv (verdict r02, row f2) could save
-  if (x_tstride == 2 && !ac) a.x_bytes = 0;
-#endif
+  const bool ac = accumulate != 0;
   const PwFwdForm f = pw_fwd_form(M, K, mask != nullptr, x_rsign, y_rsign);
   bool ok;
   if (f.smallm) {
@@ -1743,18 +1640,12 @@ int sgcn_pw_fwd_bf16(const float* w, int w_mcontig, const float* bias, const flo
                      long long x_bstride, long long x_cstride, int x_tstride, float* y,
                      long long y_bstride, long long y_cstride, int y_tstride, int y_rsign,
                      int relu, int B, int M, int K, int T, int V, void* stream) {
-  // sgcn_pw_fwd's checks (mask = NULL, x_rsign = 0)
-  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
-  SGCN_REQUIRE(x_tstride >= 1 && y_tstride >= 1);
-  SGCN_REQUIRE(y_rsign >= -1 && y_rsign <= 1);
-  SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
-  SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
-  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, x_tstride, B, K, T, V) < kPwMaxElems);
-  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, y_tstride, B, M, T, V) < kPwMaxElems);
+  const Plane xp{x, x_bstride, x_cstride, x_tstride, 0};
+  const OutPlane yp{y, y_bstride, y_cstride, y_tstride, y_rsign};
+  SGCN_REQUIRE(fwd_shape_ok(B, M, K, T, V, xp, yp));
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(w && x && y);
-  const FwdArgs a = fwd_args(w, w_mcontig, bias, {x, x_bstride, x_cstride, x_tstride, 0},
-                             {y, y_bstride, y_cstride, y_tstride, y_rsign}, relu, B, M, K, T, V);
+  const FwdArgs a = fwd_args(w, w_mcontig, bias, xp, yp, relu, B, M, K, T, V);
   SGCN_REQUIRE(launch_pwg_bf16(a, pw_fwd_bf16_form(M, K), (hipStream_t)stream));
   SGCN_LAUNCH_CHECK();
   return 0;
@@ -1768,14 +1659,12 @@ int sgcn_pw_fwd_tshift(const float* w, const float* bias, const float* x, long l
                        void* ws, size_t ws_bytes, float* y, long long y_bstride,
                        long long y_cstride, int relu, int two_row, int B, int M, int K, int T,
                        int V, void* stream) {
-  SGCN_REQUIRE(B >= 0 && M > 0 && K > 0 && K <= kPwMaxK && T >= 0 && V > 0 && V < 32768);
+  const Plane xp{x, x_bstride, x_cstride, 1, 0};
+  const OutPlane yp{y, y_bstride, y_cstride, 1, 0};
+  SGCN_REQUIRE(fwd_shape_ok(B, M, K, T, V, xp, yp));
   SGCN_REQUIRE(two_row >= 0 && two_row <= 2);
   SGCN_REQUIRE((in_scale == nullptr) == (in_shift == nullptr));
-  SGCN_REQUIRE(x_cstride * (long long)K < (1LL << 31) && y_cstride * (long long)M < (1LL << 31));
   SGCN_REQUIRE(x_cstride >= (long long)T * V && y_cstride >= (long long)T * V);
-  SGCN_REQUIRE((long long)B * T * V < (1LL << 31));
-  SGCN_REQUIRE(pw_extent(x_bstride, x_cstride, 1, B, K, T, V) < kPwMaxElems);
-  SGCN_REQUIRE(pw_extent(y_bstride, y_cstride, 1, B, M, T, V) < kPwMaxElems);
   if (B == 0 || T == 0) return 0;
   SGCN_REQUIRE(w && x && y && xpos && ypos && ws && ws_bytes >= sgcn_pw_tshift_ws_bytes(K));
   hipStream_t st = (hipStream_t)stream;
@@ -1783,8 +1672,7 @@ int sgcn_pw_fwd_tshift(const float* w, const float* bias, const float* x, long l
                                                      two_row, (int*)ws);
   tshift_two_row_flag_kernel<<<1, 256, 0, st>>>(K, (int*)ws);
   SGCN_LAUNCH_CHECK();
-  FwdArgs a = fwd_args(w, 0, bias, {x, x_bstride, x_cstride, 1, 0},
-                       {y, y_bstride, y_cstride, 1, 0}, relu, B, M, K, T, V);
+  FwdArgs a = fwd_args(w, 0, bias, xp, yp, relu, B, M, K, T, V);
   a.ts = (const int*)ws;
   a.xs = x_shifted;
   SGCN_REQUIRE(launch_pwg_tsh(a, pw_tshift_form(M), st));
@@ -1825,13 +1713,7 @@ int sgcn_pw_dw(const float* g, long long g_bstride, long long g_cstride, int g_t
   bool ok = true;
   if (f.family == DwFamily::smallc) ok = launch_dwc(a, f, st);
   else if (f.family == DwFamily::dw3) ok = launch_dw3(a, f, st);
-  else
-#ifdef SGCN_DIAG_DW64_SKIP
-    // timing bound only: the 64 x 64 weight gradients are not computed (the slabs keep
-    // whatever they held), the most a dX + dW fusion at C = 64 could remove
-    if (!(f.tile.bm == 64 && f.tile.bn == 64 && plain))
-#endif
-    ok = launch_dw(a, f, plain, st);
+  else ok = launch_dw(a, f, plain, st);
   SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   launch_slab_reduce(a.slab, a.bslab, f.S, M, Nc, dw, dw_transpose, dw_accumulate, dbias,

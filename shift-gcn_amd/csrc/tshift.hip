@@ -953,13 +953,6 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
   const unsigned vo = own ? (unsigned)tid * 4u : 0x80000000u;
   const unsigned vstep = (unsigned)NTE * 4u, nbytes = (unsigned)n * 4u;
   const size_t poff = (size_t)plane * n;
-#ifdef SGCN_DIAG_X1B_BOUND
-  // timing diagnostic only (results wrong): the shift_in backward (affine taps) of a plane
-  // of C >= SGCN_DIAG_X1B_BOUND channels reads no gout (the dAs read a fused epilogue saves)
-  const unsigned gbytes = AFFINE && !GP && C >= SGCN_DIAG_X1B_BOUND ? 0u : nbytes;
-#else
-  const unsigned gbytes = nbytes;
-#endif
   float t[LPT], rin_r[LPT];
   float zr[GBN ? LPT : 1], dr[GBD ? LPT : 1];
   {   // every global load of the plane in flight together
@@ -995,7 +988,7 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
         t[e] = k1 * gm + k2 * u2[e] + k3;
       }
     } else {
-      const auto gr = make_rsrc(gout + poff, gbytes);
+      const auto gr = make_rsrc(gout + poff, nbytes);
 #pragma unroll
       for (int e = 0; e < LPT; ++e) {
         t[e] = bload(gr, vo + e * vstep, 0);

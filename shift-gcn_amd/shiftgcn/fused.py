@@ -908,7 +908,7 @@ def _unit_backward(unit, s: UnitSaved, dout, off):
 # default no unit fuses (512 exceeds every Shift-GCN width). A/B knob (0 = every unit).
 TSHIFT_FUSION_MIN_C = int(os.environ.get("SGCN_TSHIFT_FUSION_MIN_C", "512"))
 # The fused operand's two-tap form for channels with |xpos| < 2^-25 (ops.pw_fwd_tshift
-# two_row; round 6): 2 = also 0 < xpos < 2^-25 (within 3e-8 x max|tap|), 1 = xpos in
+# two_row; round 6): 2 = also 0 < xpos < 2^-25 (within 2e-7 x max|tap|), 1 = xpos in
 # (-2^-25, 0] only (bit-identical), 0 = four taps always. A/B knob.
 TSHIFT_TWO_ROW = int(os.environ.get("SGCN_TSHIFT_TWO_ROW", "2"))
 # Inference: the eval-mode BatchNorm right after a conv (down.1 after down.0, residual.bn

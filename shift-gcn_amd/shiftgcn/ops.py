@@ -679,7 +679,7 @@ def pw_fwd_tshift(w, bias, x: PlaneView, xpos, ypos, st, out: PlaneView, M, K, T
     weight gradient). ``st``: the BnStats of Shift_tcn.bn (None = identity); w is (M, K)
     k-contiguous. ``two_row``: 0 = every channel from four taps (bit-identical to
     tshift_fwd); 1 = channels with xpos in (-2^-25, 0] from two taps of their own column
-    (still bit-identical); 2 = also 0 < xpos < 2^-25 (within 3e-8 * max|tap|)."""
+    (still bit-identical); 2 = also 0 < xpos < 2^-25 (within 2e-7 * max|tap|)."""
     check_input(w, "weight")
     _opt(bias, "bias")
     if x.tstride != 1 or x.rsign != 0 or out.tstride != 1 or out.rsign != 0:

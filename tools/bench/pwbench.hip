@@ -74,7 +74,7 @@ template <int BM, int BN, int WM, int WN, bool AR = false>
 void fwd_variant(const Shape& s, const FwdArgs& a, hipStream_t st, const float* yref,
                  double fl, double by) {
   if (a.M > BM || (AR && a.K > 64)) return;
-  const dim3 grid = pwg_grid(a, {BM, BN, WM, WN, AR});
+  const dim3 grid = pwg_grid(a, BM, BN);
   auto L = [&]() {
     with_consts([&](auto MASK, auto XROT) {
       pwg_fwd_kernel<BM, BN, WM, WN, MASK, XROT, false, false, false, AR>
