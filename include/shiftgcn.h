@@ -441,8 +441,9 @@ int sgcn_modalities(const float* joint, const int* parent, float* out_joint, flo
  *      (identity when sum|axis| < 1e-6 or |angle| < 1e-6); every joint with (x + y) + z != 0
  *      is multiplied by it in float64 and rounded to float32. Then the same with
  *      v = joint[x_right] - joint[x_left] of the Z-rotated frame 0 and the axis (1,0,0).
- * Steps 1-4 are bit-exact with the reference; step 5 differs from it by float32 rounding
- * of |v| and the device's acos/sin/cos. NaN or Inf inputs are undefined.
+ * Steps 1-4 are bit-exact with the reference; step 5 differs from it by the device's
+ * acos/sin/cos alone (|v| is the square root of the float32 squares summed exactly and
+ * rounded once, as numpy's float32 dot product gives it). NaN or Inf inputs are undefined.
  * Requires W*M <= SGCN_SEQ_MAX_WM and every joint index < V (EINVAL otherwise);
  * n_windows == 0 returns 0 without a launch. The table lives on the device, so its rows
  * cannot be checked here: a row is clamped to the sequence and to W (it never reads or

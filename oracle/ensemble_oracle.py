@@ -19,10 +19,15 @@ import torch
 MODALITIES = ("joint", "bone", "joint_motion", "bone_motion")
 
 
-def derive_modalities(joint, bone_pairs):
-    """joint: (C, T, V, M) or (N, C, T, V, M) float32 -> dict of the four streams."""
+def derive_modalities(joint, bone_pairs=None, parent=None):
+    """joint: (C, T, V, M) or (N, C, T, V, M) float32 -> dict of the four streams. The bones
+    are ``bone_pairs`` (child, parent) or a (V,) ``parent`` table (the kernel's form)."""
     j = np.asarray(joint, dtype=np.float32)
     bone = np.zeros_like(j)
+    if (bone_pairs is None) == (parent is None):
+        raise ValueError("give bone_pairs or a parent table")
+    if parent is not None:
+        bone_pairs = list(enumerate(int(p) for p in parent))
     for v, p in bone_pairs:
         bone[..., v, :] = j[..., v, :] - j[..., p, :]
     T = j.shape[-3]

@@ -51,13 +51,17 @@ __device__ __forceinline__ void rotate_present(const double* mat, float& x, floa
 }
 
 // The matrix that turns v onto the unit axis e (2: z, 0: x) about v x e: angle_between
-// (rotation.py:28-42: 0 when sum|v| < 1e-6; unit vector in float32, arccos in float64) and
+// (rotation.py:28-42: 0 when sum|v| < 1e-6; unit vector in float32, its norm the square root
+// of a float32 dot product; arccos in float64) and
 // rotation_matrix (rotation.py:5-20: identity when sum|axis| < 1e-6 or |theta| < 1e-6).
 __device__ void align_matrix(float vx, float vy, float vz, int e, double* mat) {
   double theta = 0.0;
   const float l1 = (fabsf(vx) + fabsf(vy)) + fabsf(vz);
   if (!((double)l1 < 1e-6)) {
-    const float norm = sqrtf((vx * vx + vy * vy) + vz * vz);
+    // |v| as the reference's float32 dot product gives it: the three float32 squares
+    // summed exactly (in float64) and rounded once, not once per addition
+    const float norm =
+        sqrtf((float)(((double)(vx * vx) + (double)(vy * vy)) + (double)(vz * vz)));
     const float u = (e == 2 ? vz : vx) / norm;
     theta = acos(fmin(fmax((double)u, -1.0), 1.0));
   }
