@@ -54,7 +54,9 @@ extern "C" {
  * sequence cut, padded and pre-normalised on the device) and sgcn_window_aggregate (window
  * scores averaged per frame). Added within 25 (additive, no entry changed):
  * sgcn_pw_fwd_bf16 (eval-mode bf16-operand contractions) and sgcn_clip_augment (the feeder's
- * training augmentations on the device). */
+ * training augmentations on the device); sgcn_bn_bwd_apply_tsh, and sgcn_tshift_bwd_gbn
+ * accepting gin = NULL (shift_in's input gradient inside a unit is never stored: the
+ * sums-only form, and the apply that re-forms the gradient from gout). */
 int sgcn_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -183,7 +185,9 @@ int sgcn_tshift_bwd_f64(const double* gout, const double* in, const double* xpos
  * BatchNorm's backward sums without a reduce pass either.
  * H*W <= 16384, W <= 64 and at most 32 elements per thread of the joint-aligned stride
  * (NT / W) * W, NT = 256 (H*W <= 8192; 512 if 256 would need more than 32) or 512 (else
- * SGCN_EINVAL: use sgcn_tshift_bwd + sgcn_bn_bwd_reduce). */
+ * SGCN_EINVAL: use sgcn_tshift_bwd + sgcn_bn_bwd_reduce).
+ * gin = NULL (added within ABI 25): the sums-only form. Every partial, gx and gy as with gin (bit for
+ * bit), and gin is not stored; sgcn_bn_bwd_apply_tsh re-forms it from gout. */
 int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
                         const float* ypos, const float* in_scale, const float* in_shift,
                         const float* bn_mean, const float* bn_invstd, float* bn_part,
@@ -352,6 +356,17 @@ int sgcn_bn_bwd_apply(const float* dy, const float* y, int relu, const float* x,
                       const float* coef, int per_joint, const float* r, const float* rcoef,
                       const float* dy_coef, float* dx, float* dr, int B, int C, int T, int V,
                       void* stream);
+
+/* sgcn_bn_bwd_apply(dy = gin, y, relu = 1, x, coef, per_joint = 3, r, rcoef, dy_coef, dx, dr)
+ * with gin = the input gradient sgcn_tshift_bwd_gbn(gout, .., xpos, ypos) would have stored,
+ * re-formed per element from the gout plane (staged in LDS as that entry stages it) and never
+ * read from memory: dx and dr are bit-identical to that pair of calls. dr is required
+ * (rcoef NULL: dr = g; else with r: rk1*g + rk2*r + rk3), dy_coef too. The planes of
+ * sgcn_tshift_bwd_gbn (else SGCN_EINVAL: use the pair). */
+int sgcn_bn_bwd_apply_tsh(const float* gout, const float* xpos, const float* ypos,
+                          const float* y, const float* x, const float* coef, const float* r,
+                          const float* rcoef, const float* dy_coef, float* dx, float* dr, int B,
+                          int C, int T, int V, void* stream);
 
 /* m = tanh(Feature_Mask) + 1 (shift_gcn.py:129); n = V*C. */
 int sgcn_mask_prep(const float* mask, float* m, int n, void* stream);

@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "dispatch.hpp"
 #include "launch_forms.hpp"
+#include "shift_stage.hpp"
 
 namespace sgcn {
 namespace {
@@ -874,6 +875,102 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_ja_kernel(
   }
 }
 
+// bn_bwd_apply_ja_kernel<.., 3, true, RES, true> whose dy is never read from memory: dy =
+// shift_inᵀ(gout), the input gradient of Shift_tcn's stride-1 shift_in (positions xpos, ypos),
+// re-formed per element from the gout plane staged in the zero-padded LDS image exactly as
+// tshift_bwd_ra_kernel stages it, through the same shift_in_grad — so the tensor that kernel
+// would store and this one read back never exists, and dx / dr are bit-identical to the pair
+// (same expressions in the same order from there on). One workgroup per (b, c) plane on
+// the joint-aligned stride; y, x (and r) in registers, every load in flight before the
+// barrier. A channel whose taps leave the padding takes a rolled, range-checked loop that
+// re-reads its operands (never in a trained model).
+template <int NT, int LPT, int RES>
+__global__ __launch_bounds__(NT) void bn_bwd_apply_tsh_kernel(
+    const float* __restrict__ gout, const float* __restrict__ xpos,
+    const float* __restrict__ ypos, const float* __restrict__ y, const float* __restrict__ x,
+    const float* __restrict__ coef, int F, const float* __restrict__ r,
+    const float* __restrict__ rcoef, int RF, const float* __restrict__ dyc,
+    float* __restrict__ dx, float* __restrict__ dr, int C, int T, int V) {
+  SGCN_CRIT_PRIO();
+  static_assert(RES == 1 || RES == 2, "dr = g, or the down BatchNorm's input gradient");
+  extern __shared__ float lds[];   // [(T + 2*kPadRows) * WP] padded gout + 1 spare
+  const int plane = blockIdx.x, c = plane % C, rc = c % V;
+  const int WP = V + 2, GR = NT / V, NTJ = GR * V, tid = threadIdx.x;
+  const bool own = tid < NTJ;
+  const int w = tid % V, h0 = tid / V;
+  const int P = T * V;
+  const size_t off = (size_t)plane * P;
+  const unsigned vo = own ? (unsigned)tid * 4u : 0x80000000u, vstep = (unsigned)NTJ * 4u;
+  const unsigned pb = (unsigned)P * 4u;
+  int wz = w - rc;
+  wz = wz < 0 ? wz + V : wz;
+  const unsigned go = vo + (unsigned)((wz - w) * 4);   // dx (and x) index
+  const auto yr = make_rsrc(y + off, pb);
+  const auto xr = make_rsrc(x + off, pb);
+  const auto rr = make_rsrc(RES == 2 ? r + off : y + off, RES == 2 ? pb : 0u);
+  float yv[LPT], xv[LPT], rv[RES == 2 ? LPT : 1];
+  {
+    const auto gr = make_rsrc(gout + off, pb);
+    float t[LPT];
+#pragma unroll
+    for (int e = 0; e < LPT; ++e) t[e] = bload(gr, vo + e * vstep, 0);
+#pragma unroll
+    for (int e = 0; e < LPT; ++e) {
+      yv[e] = bload(yr, vo + e * vstep, 0);
+      xv[e] = bload(xr, go + e * vstep, 0);
+    }
+    if (RES == 2) {
+#pragma unroll
+      for (int e = 0; e < LPT; ++e) rv[e] = bload(rr, vo + e * vstep, 0);
+    }
+    zero_pad<NT>(lds, T, V);
+    // element (h, w) at lds[(h + kPadRows) * WP + w + 1]; a lane's elements past the plane go
+    // to the spare float after the padded plane (branch-free stores)
+    const int lb = (h0 + kPadRows) * WP + w + 1, lspare = ra_pad_floats(T, V);
+#pragma unroll
+    for (int e = 0; e < LPT; ++e)
+      lds[own && e * NTJ + tid < P ? lb + e * GR * WP : lspare] = t[e];
+  }
+  const int f = c * V + w;
+  const float k1 = coef[f], k2 = coef[F + f], k3 = coef[2 * F + f];
+  const float d1 = dyc[c], d2 = dyc[C + c], d3 = dyc[2 * C + c];
+  float q1 = 0.f, q2 = 0.f, q3 = 0.f;
+  if (RES == 2) { q1 = rcoef[c]; q2 = rcoef[RF + c]; q3 = rcoef[2 * RF + c]; }
+  const Geom rg = make_geom(-xpos[c], -ypos[c]);
+  const auto dxr = make_rsrc(dx + off, pb);
+  const auto drr = make_rsrc(dr + off, pb);
+  __syncthreads();
+  if (!own) return;
+  const int lmax = (T - 1 + kPadRows) * WP + V;   // the last element: bases past the plane clamp here
+  if (shift_in_grad_fits(rg)) {
+    int l0 = (h0 + kPadRows) * WP + w + 1;
+#pragma unroll
+    for (int e = 0; e < LPT; ++e) {
+      float g = shift_in_grad<true>(lds, rg, min(l0, lmax), 0, w, T, V);
+      g = d1 * g + d2 * yv[e] + d3;
+      g = yv[e] > 0.f ? g : 0.f;
+      bstore(dxr, k1 * g + k2 * xv[e] + k3, go + e * vstep, 0);
+      if (RES == 1) bstore(drr, g, vo + e * vstep, 0);
+      if (RES == 2) bstore(drr, q1 * g + q2 * rv[e] + q3, vo + e * vstep, 0);
+      // (the next base opaque to the compiler, as in tshift_bwd_ra_kernel: no long-lived
+      // address register per element)
+      l0 += GR * WP;
+      asm volatile("" : "+v"(l0));
+    }
+  } else {
+#pragma unroll 1
+    for (int e = 0; e < LPT; ++e) {
+      const float yy = bload(yr, vo + e * vstep, 0), xx = bload(xr, go + e * vstep, 0);
+      float g = shift_in_grad<false>(lds, rg, 0, h0 + e * GR, w, T, V);
+      g = d1 * g + d2 * yy + d3;
+      g = yy > 0.f ? g : 0.f;
+      bstore(dxr, k1 * g + k2 * xx + k3, go + e * vstep, 0);
+      if (RES == 1) bstore(drr, g, vo + e * vstep, 0);
+      if (RES == 2) bstore(drr, q1 * g + q2 * bload(rr, vo + e * vstep, 0) + q3, vo + e * vstep, 0);
+    }
+  }
+}
+
 // Plane-resident form of gcn_dx_finish_kernel (V <= 64, <= 32 elements per thread): the
 // same one-pass assignment (a thread owns destination joint v' and so source joint
 // u = (v' - c) mod V: one mask value, one dmask accumulator), with the whole plane's loads
@@ -1366,6 +1463,31 @@ int sgcn_bn_bwd_apply(const float* dy, const float* y, int relu, const float* x,
   const bool ok = per_joint == 3
                       ? launch_plane(T, V, ja, loop, Const<3>{}, Const<true>{}, rs, dyt)
                       : launch_plane(T, V, ja, loop, Const<0>{}, relu != 0, rs, dyt);
+  SGCN_REQUIRE(ok);
+  SGCN_LAUNCH_CHECK();
+  return 0;
+}
+
+int sgcn_bn_bwd_apply_tsh(const float* gout, const float* xpos, const float* ypos,
+                          const float* y, const float* x, const float* coef, const float* r,
+                          const float* rcoef, const float* dy_coef, float* dx, float* dr, int B,
+                          int C, int T, int V, void* stream) {
+  SGCN_REQUIRE(B > 0 && C > 0 && T > 0 && V > 0);
+  SGCN_REQUIRE(gout && xpos && ypos && y && x && coef && dy_coef && dx && dr);
+  SGCN_REQUIRE((r == nullptr) == (rcoef == nullptr));
+  SGCN_REQUIRE((long long)B * C < (1LL << 31));
+  // the planes and the (threads, elements per thread) of sgcn_tshift_bwd_gbn, whose staging
+  // this is (caller falls back to the stored gradient: ops.ra_fits)
+  const LaunchForm f = gbn_form(T, V, r != nullptr);
+  SGCN_REQUIRE(f.kind == Kind::ra);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = ra_lds_bytes(T, V, f.nt, false);
+  auto go = [&](auto NT, auto LPT, auto RES) {
+    bn_bwd_apply_tsh_kernel<NT, LPT, RES><<<B * C, int(NT), lds, st>>>(
+        gout, xpos, ypos, y, x, coef, C * V, r, rcoef, C, dy_coef, dx, dr, C, T, V);
+  };
+  const bool ok = r ? with_form<kGbdForms>({f.nt, f.lpt}, go, Const<2>{})
+                    : with_form<kRaForms>({f.nt, f.lpt}, go, Const<1>{});
   SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   return 0;

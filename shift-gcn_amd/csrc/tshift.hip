@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "dispatch.hpp"
 #include "launch_forms.hpp"
+#include "shift_stage.hpp"
 
 #pragma clang fp contract(off)
 
@@ -39,27 +40,7 @@ namespace {
 // the contraction that consumes its output (front to back) then starts on the planes it
 // wrote last.
 
-struct Geom {
-  int x1, y1;
-  float dx, dy;
-};
-
-// `int x1 = floorf(x); dx = x - x1;` (.cu:49-71)
-__device__ __forceinline__ Geom make_geom(float x, float y) {
-  Geom g;
-  g.x1 = (int)floorf(x);
-  g.y1 = (int)floorf(y);
-  g.dx = x - (float)g.x1;
-  g.dy = y - (float)g.y1;
-  return g;
-}
-
-// q11*(1-dx)*(1-dy) + q21*dx*(1-dy) + q12*(1-dx)*dy + q22*dx*dy, left to right (.cu:73)
-__device__ __forceinline__ float blend(float q11, float q21, float q12, float q22, float dx,
-                                       float dy) {
-  const float omdx = 1.f - dx, omdy = 1.f - dy;
-  return q11 * omdx * omdy + q21 * dx * omdy + q12 * omdx * dy + q22 * dx * dy;
-}
+// (Geom, make_geom, blend, zero_pad: shift_stage.hpp)
 
 // Position of element `o` of a W-wide plane, advanced by blockDim per step without
 // integer division in the loop.
@@ -324,23 +305,6 @@ __global__ __launch_bounds__(kThreads) void tshift_bwd_kernel(
 // ------------------------------------------------------------------------------------
 // (plane limits kFwdLdsMax / kFwdLdsMax2 / kBwdLdsMax and the zero-padded LDS plane layout,
 // kPadRows / ra_pad_floats: launch_forms.hpp)
-
-// zero the padding of a padded H x W plane (NT threads)
-template <int NT>
-__device__ __forceinline__ void zero_pad(float* lds, int H, int W) {
-  const int WP = W + 2, nprow = 2 * kPadRows * WP;
-  for (int i = (int)threadIdx.x; i < nprow + 2 * H; i += NT) {
-    int a;
-    if (i < nprow) {
-      const int r = i / WP, col = i - r * WP;
-      a = (r < kPadRows ? r : H + r) * WP + col;
-    } else {
-      const int j = i - nprow;
-      a = ((j >> 1) + kPadRows) * WP + ((j & 1) ? W + 1 : 0);
-    }
-    lds[a] = 0.f;
-  }
-}
 
 // copy n floats src -> lds (optionally x*a+b), all loads of a thread issued before any
 // LDS store; n <= LPT * NT
@@ -922,8 +886,11 @@ __global__ __launch_bounds__(NT) void tshift_bwd_s2_kernel(
 // H > 0, dh = (d - d_mean[c]) * d_invstd[c], to gdpart[j][plane] — the same six-sum form,
 // finalized by sgcn_bn_bwd_finalize_gbn with V = 1 — so no sgcn_bn_bwd_reduce pass over
 // (dA, H, Z, d) remains for the units with a down conv either.
+// STORE = false (GBN only): the sums-only form. Everything above except the gin store: the
+// consumer of gin re-forms it from gout with the same shift_in_grad (sgcn_bn_bwd_apply_tsh),
+// so the tensor never exists. Every sum is bit-identical to the storing form's.
 template <int NT, int LPT, bool AFFINE, bool RELU_MASK, bool BNP, int GP, bool GBN,
-          bool GBD = false>
+          bool GBD = false, bool STORE = true>
 __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
     const float* __restrict__ gout, const float* __restrict__ in,
     const float* __restrict__ xpos, const float* __restrict__ ypos,
@@ -939,6 +906,7 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
   SGCN_CRIT_PRIO();
   static_assert(!GBN || (AFFINE && BNP && !GP), "GBN: shift_in with BNP");
   static_assert(!GBD || GBN, "GBD extends GBN");
+  static_assert(STORE || GBN, "sums only: the GBN forms");
   extern __shared__ float lds[];   // [(H + 2*kPadRows) * WP] padded gout (GBN: >= 6*NT)
   __shared__ float red[4 * NT / 64];
   const int plane = gridDim.x - 1 - blockIdx.x;   // reverse: see kReverse note
@@ -1036,7 +1004,7 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
   const Geom g = make_geom(x, y);
   const bool fits = r.y1 >= -kPadRows && r.y1 <= kPadRows - 1 && g.y1 >= -kPadRows &&
                     g.y1 <= kPadRows - 1 && r.x1 >= -1 && r.x1 <= 0 && g.x1 >= -1 && g.x1 <= 0;
-  const int kq = r.y1 * WP + r.x1, kg = (-g.y1 - 1) * WP - g.x1 - 1;
+  const int kg = (-g.y1 - 1) * WP - g.x1 - 1;
   const int nfull = n / NTE;     // elements e < nfull are inside the plane for every lane
   const int lmax = (H - 1 + kPadRows) * WP + W;   // the last element: past-the-plane bases clamp here
   const auto gir = make_rsrc(gin + poff, nbytes);
@@ -1045,14 +1013,12 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
   float d6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // GBD plane sums
   // one element: value, stores and sums from its eight taps (tail: the element may lie
   // past the plane — its load returned 0, its store drops, its sums are masked here)
-  auto elem = [&](int e, bool tail, float q11, float q21, float q12, float q22, float G11,
-                  float G21, float G12, float G22) {
+  auto elem = [&](int e, bool tail, float val, float G11, float G21, float G12, float G22) {
     const bool ok = !tail || e * NTE + tid < n;
-    float val = blend(q11, q21, q12, q22, r.dx, r.dy);
     const float rin = rin_r[e];
     if (RELU_MASK) val = rin > 0.f ? val : 0.f;
     if (tail) val = ok ? val : 0.f;
-    bstore(gir, val, vo + e * vstep, 0);   // (an immediate-offset store off one base)
+    if (STORE) bstore(gir, val, vo + e * vstep, 0);   // (an immediate-offset store off one base)
     if (GBN) {
       // predicated, not branched (a branch per element keeps every element's registers
       // live across the blocks): an inactive element adds exact +0 to sums that are
@@ -1095,9 +1061,9 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
     for (int e = 0; e < LPT; ++e) {
       const bool tail = e >= nfull;
       const int lt = min(l0, lmax);   // (an in-plane element's base never exceeds lmax)
-      const int la = lt + kq, lg = lt + kg;
-      elem(e, tail, lds[la], lds[la + 1], lds[la + WP], lds[la + WP + 1], lds[lg + WP + 1],
-           lds[lg + WP], lds[lg + 1], lds[lg]);
+      const int lg = lt + kg;
+      elem(e, tail, shift_in_grad<true>(lds, r, lt, 0, w, H, W), lds[lg + WP + 1], lds[lg + WP],
+           lds[lg + 1], lds[lg]);
       // the next element's base is opaque to the compiler: its address arithmetic (and so
       // its LDS reads) cannot be hoisted into one long-lived register per element
       l0 += lstep;
@@ -1122,12 +1088,11 @@ __global__ __launch_bounds__(NT) void tshift_bwd_ra_kernel(
       const bool ok = e * NTE + tid < n;
       const float rin = bload(inr, vo + e * vstep, 0);
       const float zv = GBN ? bload(zrr, vo + e * vstep + (unsigned)((wz - w) * 4), 0) : 0.f;
-      const int rq = h + r.y1, cq = w + r.x1, rg = h - g.y1 - 1, cg = w - g.x1 - 1;
-      float val = blend(tap(rq, cq), tap(rq, cq + 1), tap(rq + 1, cq), tap(rq + 1, cq + 1),
-                        r.dx, r.dy);
+      const int rg = h - g.y1 - 1, cg = w - g.x1 - 1;
+      float val = shift_in_grad<false>(lds, r, 0, h, w, H, W);
       if (RELU_MASK) val = rin > 0.f ? val : 0.f;
       val = ok ? val : 0.f;
-      bstore(gir, val, vo + e * vstep, 0);
+      if (STORE) bstore(gir, val, vo + e * vstep, 0);
       if (GBN && rin > 0.f) {
         const float hc = rin - bmu, zh = (zv - zm) * zi;
         a6[0] += val;
@@ -1285,12 +1250,12 @@ struct RaArgs {
 };
 
 // launch tshift_bwd_ra_kernel on f's (threads, elements per thread), one of Forms, with the
-// flags AFFINE, RELU, BNP, GP, GBN, GBD (dispatch.hpp); false: nothing launched
+// flags AFFINE, RELU, BNP, GP, GBN, GBD, STORE (dispatch.hpp); false: nothing launched
 template <const auto& Forms, class... A>
 bool launch_ra(const LaunchForm& f, const RaArgs& a, hipStream_t st, A... flags) {
   return with_form<Forms>({f.nt, f.lpt}, [&](auto NT, auto LPT, auto AFFINE, auto RELU, auto BNP,
-                                           auto GP, auto GBN, auto GBD) {
-    tshift_bwd_ra_kernel<NT, LPT, AFFINE, RELU, BNP, GP, GBN, GBD>
+                                           auto GP, auto GBN, auto GBD, auto STORE) {
+    tshift_bwd_ra_kernel<NT, LPT, AFFINE, RELU, BNP, GP, GBN, GBD, STORE>
         <<<a.B * a.C, int(NT), ra_lds_bytes(a.H, a.W, NT, GBN), st>>>(
             a.gout, a.in, a.xpos, a.ypos, a.scale, a.shift, a.bmu, a.bis, a.gin, a.pg, a.bp, a.C,
             a.H, a.W, a.gdy, a.gy, a.gx, a.gcoef, a.gz, a.gzm, a.gzi, a.gzpart, a.gd, a.gdm,
@@ -1444,7 +1409,8 @@ int sgcn_tshift_bwd_bnin(const float* dy, const float* y, const float* s, const 
   a.gdyp = dy_plane != 0;
   // y == NULL: dy already carries the ReLU mask (GP = 2: the y plane is not loaded)
   const bool ok = launch_ra<kBninForms>(f, a, st, Const<false>{}, Const<true>{}, Const<false>{},
-                                        OneOf<1, 2>{y ? 1 : 2}, Const<false>{}, Const<false>{});
+                                        OneOf<1, 2>{y ? 1 : 2}, Const<false>{}, Const<false>{},
+                                        Const<true>{});
   SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
@@ -1498,7 +1464,7 @@ int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
   const LaunchForm f = gbn_form(H, W, d != nullptr);
   SGCN_REQUIRE(f.kind == Kind::ra);
   SGCN_REQUIRE(gout && in && xpos && ypos && in_scale && in_shift && bn_mean && bn_invstd &&
-               bn_part && z && z_mean && z_invstd && z_part && gin && ws);
+               bn_part && z && z_mean && z_invstd && z_part && ws);
   SGCN_REQUIRE((gx == nullptr) == (gy == nullptr));
   SGCN_REQUIRE(ws_bytes >= sgcn_tshift_bwd_ws_bytes(B, C));
   SGCN_REQUIRE((long long)B * C < (1LL << 31));
@@ -1518,8 +1484,10 @@ int sgcn_tshift_bwd_gbn(const float* gout, const float* in, const float* xpos,
   }
   const Const<true> on{};
   const Const<false> off{};
-  const bool ok = d ? launch_ra<kGbdForms>(f, a, st, on, off, on, Const<0>{}, on, on)
-                    : launch_ra<kRaForms>(f, a, st, on, off, on, Const<0>{}, on, off);
+  // gin == NULL: the sums-only form (its consumer re-forms gin: sgcn_bn_bwd_apply_tsh)
+  const bool store = gin != nullptr;
+  const bool ok = d ? launch_ra<kGbdForms>(f, a, st, on, off, on, Const<0>{}, on, on, store)
+                    : launch_ra<kRaForms>(f, a, st, on, off, on, Const<0>{}, on, off, store);
   SGCN_REQUIRE(ok);
   SGCN_LAUNCH_CHECK();
   if (gx) tshift_pos_finalize_kernel<<<(C + 3) / 4, 256, 0, st>>>(pg, B, C, gx, gy);
@@ -1550,7 +1518,8 @@ int sgcn_tshift_bwd(const float* gout, const float* in, const float* xpos, const
   if (f.kind == Kind::ra) {
     const RaArgs a{gout, in, xpos, ypos, in_scale, in_shift, bn_mean, bn_invstd, gin, pg, bp, B,
                    C, H, W};
-    ok = launch_ra<kRaForms>(f, a, st, aff, relu, bnp, Const<0>{}, Const<false>{}, Const<false>{});
+    ok = launch_ra<kRaForms>(f, a, st, aff, relu, bnp, Const<0>{}, Const<false>{}, Const<false>{},
+                             Const<true>{});
   } else if (f.kind == Kind::s2) {   // f.flag: joint-aligned walk (W <= 64)
     const size_t lds = (size_t)(H + Ho) * W * sizeof(float);
     ok = with_consts([&](auto LPT, auto JA, auto AFFINE, auto RELU, auto BNP) {

@@ -71,6 +71,8 @@ SIGNATURES = {
     "sgcn_bn_bwd_finalize": (_I, [_P, _I, _I, _L, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "sgcn_bn_bwd_apply": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I,
                                _P]),
+    "sgcn_bn_bwd_apply_tsh": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
+                                   _P]),
     "sgcn_mask_prep": (_I, [_P, _P, _I, _P]),
     "sgcn_gcn_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "sgcn_gcn_dx_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I,
@@ -124,7 +126,8 @@ def _open(path):
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            # an entry added within the ABI version (sgcn_pw_fwd_bf16, sgcn_clip_augment)
+            # an entry added within the ABI version (sgcn_pw_fwd_bf16, sgcn_clip_augment,
+            # sgcn_bn_bwd_apply_tsh)
             raise NativeLibraryError(
                 f"{path} (ABI {abi}) has no {name}: it was built from an older tree; "
                 "rebuild it") from None

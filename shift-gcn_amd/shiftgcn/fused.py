@@ -21,6 +21,8 @@ Shift_tcn (shift_gcn.py:65-74)
         -> pw_dw -> tshift_bwd[bn affine + bn-backward partials fused] -> finalize
         -> (standalone: bn_bwd_apply; in a unit the BN input gradient is never written: the
            gcn BN-backward kernels evaluate it on the fly)
+        (in a unit the shift_in backward keeps its sums only, DA_REFORM: its input gradient
+        is re-formed from dAs by the gcn BN backward apply, bn_bwd_apply_tsh)
 TCN_GCN_unit (shift_gcn.py:160-162): bn2 apply + residual (0 / identity / tcn conv+BN) +
   ReLU is ONE bn_apply launch; its backward ONE reduce + ONE apply.
 Neighbouring units of a chain (shift_gcn.linked_units) share launches: a unit's tail writes
@@ -360,13 +362,25 @@ def prepare_masks(gcns):
     return [(fm, fm._version, m) for fm, m in zip(fms, ms)]
 
 
+class ShiftGrad:
+    """An input gradient of Shift_tcn.shift_in that was not stored: ``gout`` (the shift's
+    output gradient) and the shift's positions; its consumer re-forms it element by element
+    (ops.bn_bwd_apply_tsh). Made by tcn_core_backward, taken by gcn_backward as ``dH``."""
+
+    __slots__ = ("gout", "xpos", "ypos")
+
+    def __init__(self, gout, xpos, ypos):
+        self.gout, self.xpos, self.ypos = gout, xpos, ypos
+
+
 def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, pre6=None,
                  off=False, mask_dx=False):
     """Returns (dx0, {param_name: grad}, prev_part). With ``dy_coef`` ([3, Cout]) the
     incoming gradient is dH = k1*dH_arg + k2*H + k3 (Shift_tcn.bn's input gradient),
     evaluated on the fly by the BN-backward kernels instead of being materialised. ``pre6``
     = (six-sum partials, Shift_tcn.bn stats) from sgcn_tshift_bwd_gbn: bn's backward
-    partials were made by the shift_in backward launch (no reduce pass here). ``off``:
+    partials were made by the shift_in backward launch (no reduce pass here); only then may
+    ``dH`` be a ShiftGrad (the apply re-forms the gradient from the shift's gout). ``off``:
     the weight-gradient launches go to the side stream (see _OffPath). ``mask_dx``: dx0 is
     returned as dx0 * (x0 > 0) (only without a down conv, whose dx is accumulated after).
     ``extra_dx`` = (tensor, its ReLU-mask operand or None), added into dx0. ``prev`` = (S, bn2
@@ -377,6 +391,8 @@ def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, p
     Cout = mod.out_channels
     g = {}
     rpart = None
+    reform = isinstance(dH, ShiftGrad)
+    assert not reform or pre6 is not None
     if pre6 is not None:
         assert dy_coef is not None and (pre6[2] is not None) == mod.has_down
         coefZ, g["bn.weight"], g["bn.bias"] = ops.bn_bwd_finalize_gbn(
@@ -401,11 +417,19 @@ def gcn_backward(mod, s: GcnSaved, dH, extra_dx=None, dy_coef=None, prev=None, p
             coefD, g["down.1.weight"], g["down.1.bias"] = ops.bn_bwd_finalize(
                 rpart, B, Cout, B * T * V, s.dst, bnd)
         dD0 = _empty(B, Cout, T, V, like=x0)
-        ops.bn_bwd_apply(dH, s.H, True, s.Z, coefZ, 3, r=s.D0, rcoef=coefD, dr=dD0, dx=dZ,
-                         dy_coef=dy_coef)
+        if reform:
+            ops.bn_bwd_apply_tsh(dH.gout, dH.xpos, dH.ypos, s.H, s.Z, coefZ, dy_coef, r=s.D0,
+                                 rcoef=coefD, dr=dD0, dx=dZ)
+        else:
+            ops.bn_bwd_apply(dH, s.H, True, s.Z, coefZ, 3, r=s.D0, rcoef=coefD, dr=dD0, dx=dZ,
+                             dy_coef=dy_coef)
     else:
         g_id = _empty(B, Cin, T, V, like=x0)
-        ops.bn_bwd_apply(dH, s.H, True, s.Z, coefZ, 3, dr=g_id, dx=dZ, dy_coef=dy_coef)
+        if reform:
+            ops.bn_bwd_apply_tsh(dH.gout, dH.xpos, dH.ypos, s.H, s.Z, coefZ, dy_coef, dr=g_id,
+                                 dx=dZ)
+        else:
+            ops.bn_bwd_apply(dH, s.H, True, s.Z, coefZ, 3, dr=g_id, dx=dZ, dy_coef=dy_coef)
     # dZ is stored in Z's pre-shift_out layout, so the einsum/bias grads and dX read it as
     # a plain plane: G(b,d,n) = dZ[b,d,n]
     dLW = ops.grad_like(mod.Linear_weight)
@@ -566,7 +590,8 @@ def tcn_core_backward(mod, s: TcnSaved, dS, materialize_dx=True, gpre=None, gcn_
                       off=False):
     """dS: gradient w.r.t. S (pre-bn2). Returns (dH, grads, pre6), or ((dA, coef), grads,
     pre6) with ``materialize_dx=False`` (dH = coef[0]*dA + coef[1]*H + coef[2], fused
-    downstream). ``gcn_z`` = (Z, zst[, (D0, dst)]) of the producing Shift_gcn: its
+    downstream; with the GBN launch and DA_REFORM dA is a ShiftGrad: shift_in's input
+    gradient is not stored, gcn_backward's apply re-forms it from dAs). ``gcn_z`` = (Z, zst[, (D0, dst)]) of the producing Shift_gcn: its
     BatchNorm's (and its down BatchNorm's) backward sums come out of the shift_in backward
     launch, returned as pre6 = (z sums, Shift_tcn.bn stats, down sums or None); else pre6
     is None."""
@@ -599,10 +624,13 @@ def tcn_core_backward(mod, s: TcnSaved, dS, materialize_dx=True, gpre=None, gcn_
     # the Shift_gcn BatchNorm that produced H)
     if gcn_z is not None and GBN_FUSION and si.stride == 1 and ops.ra_fits(T * V, V):
         down = gcn_z[2] if len(gcn_z) > 2 else None
+        reform = bool(DA_REFORM) and not materialize_dx
         res = ops.tshift_bwd_gbn(dAs, H, si.xpos.detach(), si.ypos.detach(), s.ast, gcn_z[0],
                                  gcn_z[1], defer_pos=off, down=down,
-                                 pos_out=_pos_alloc(si, off))
+                                 pos_out=_pos_alloc(si, off), store=not reform)
         dA, gx, gy, part, zpart = res[:5]
+        if reform:
+            dA = ShiftGrad(dAs, si.xpos.detach(), si.ypos.detach())
         pre6 = (zpart, s.ast, res[5] if down is not None else None)
     else:
         dA, gx, gy, part = ops.tshift_bwd(
@@ -931,6 +959,11 @@ ASYNC_DW = int(os.environ.get("SGCN_ASYNC_DW", "1"))
 # pool's expanded gradient is never written (_unit_backward, _unit_dy_planes). Bit-identical.
 # A/B knob: 0 = every consumer re-reads the output for its mask, as before.
 PREMASK = int(os.environ.get("SGCN_PREMASK", "1"))
+
+# Shift_tcn.shift_in's input gradient inside a unit is never stored: the GBN launch keeps its
+# sums only and the gcn BatchNorm backward apply re-forms the gradient from the staged dAs
+# plane (ops.bn_bwd_apply_tsh). Bit-identical. A/B knob: 0 = the stored tensor, as before.
+DA_REFORM = int(os.environ.get("SGCN_DA_REFORM", "1"))
 
 # Eval-mode inference precision (DESIGN.md §Reduced-precision inference). "bf16": the forward
 # contractions of eval blocks that no backward can follow round both operands to bf16 while

@@ -459,13 +459,14 @@ def ra_fits(n, V):
 
 
 def tshift_bwd_gbn(gout, inp, xpos, ypos, st: "BnStats", z, zst: "BnStats", defer_pos=False,
-                   down=None, pos_out=None):
+                   down=None, pos_out=None, store=True):
     """Shift_tcn.shift_in backward (stride 1, Shift_tcn.bn's affine on the taps and its
     backward partials) that also emits the k-free backward sums of Shift_gcn.bn, whose
     input is ``z`` and whose ReLU output is ``inp`` (sgcn_tshift_bwd_gbn). ``down`` =
     (d, d_stats): the Shift_gcn's down conv output and its BatchNorm's statistics — the
     six plane sums of that BatchNorm's backward come out of the same launch. Returns
-    (grad_input, grad_xpos, grad_ypos, bn_part, z_part6[, d_part6])."""
+    (grad_input, grad_xpos, grad_ypos, bn_part, z_part6[, d_part6]). ``store=False``: the
+    sums-only form, grad_input is None (its consumer re-forms it: bn_bwd_apply_tsh)."""
     check_input(gout, "grad_output")
     check_input(inp, "input")
     check_input(z, "z")
@@ -474,7 +475,7 @@ def tshift_bwd_gbn(gout, inp, xpos, ypos, st: "BnStats", z, zst: "BnStats", defe
     B, C, H, W = inp.shape
     lib = _lib.load()
     dev = inp.device
-    gin = torch.empty_like(inp)
+    gin = torch.empty_like(inp) if store else None
     nbytes = lib.sgcn_tshift_bwd_ws_bytes(B, C)
     ws = torch.empty((max(nbytes, 4) + 3) // 4, device=dev, dtype=_F32)
     gx, gy, pp = _pos_out(defer_pos, ws, B, C, dev, pos_out)
@@ -484,7 +485,8 @@ def tshift_bwd_gbn(gout, inp, xpos, ypos, st: "BnStats", z, zst: "BnStats", defe
     if down is not None:
         d, dst = down
         dpart = torch.empty((6 * B * C,), device=dev, dtype=_F32)
-    nb = 4 * (gout.numel() + (3 if down is None else 4) * inp.numel())
+    # reads: gout, inp, z (and d); write: gin unless sums-only
+    nb = 4 * (gout.numel() + (2 + (down is not None) + bool(store)) * inp.numel())
     with _timed("tshift_bwd", 0, nb, inp, ("GBND " if down is not None else "GBN ") + _shp(inp)):
         rc = lib.sgcn_tshift_bwd_gbn(_ptr(gout), _ptr(inp), _ptr(xpos), _ptr(ypos),
                                      _ptr(st.scale), _ptr(st.shift), _ptr(st.mean),
@@ -876,6 +878,30 @@ def bn_bwd_apply(dy, y, relu, x, coef, per_joint, r=None, rcoef=None, dr=None, d
             _ptr(rcoef), _ptr(dy_coef), _ptr(dx), _ptr(dr), B, C, T, V, _stream(x))
     _lib.check(rc, "sgcn_bn_bwd_apply")
     return dx
+
+
+def bn_bwd_apply_tsh(gout, xpos, ypos, y, x, coef, dy_coef, r=None, rcoef=None, dr=None,
+                     dx=None):
+    """bn_bwd_apply(dy, y, True, x, coef, 3, r, rcoef, dr, dx, dy_coef) with dy = the input
+    gradient of the stride-1 shift (xpos, ypos) whose output gradient is ``gout``, re-formed in
+    the kernel and never stored (sgcn_bn_bwd_apply_tsh; the planes ra_fits accepts). Returns
+    (dx, dr), bit-identical to tshift_bwd_gbn + bn_bwd_apply."""
+    for t, n in ((gout, "grad_output"), (y, "y"), (x, "x"), (coef, "coef"),
+                 (dy_coef, "dy_coef")):
+        check_input(t, n)
+    if (r is None) != (rcoef is None):
+        raise ValueError("r and rcoef go together")
+    B, C, T, V = x.shape
+    dx = torch.empty_like(x) if dx is None else dx
+    dr = torch.empty_like(x) if dr is None else dr
+    # reads: gout, y, x (and r); writes: dx, dr
+    nb = 4 * x.numel() * (5 + (r is not None))
+    with _timed("bn_bwd_apply", 0, nb, x, "TSH " + _shp(x)):
+        rc = _lib.load().sgcn_bn_bwd_apply_tsh(
+            _ptr(gout), _ptr(xpos), _ptr(ypos), _ptr(y), _ptr(x), _ptr(coef), _ptr(r),
+            _ptr(rcoef), _ptr(dy_coef), _ptr(dx), _ptr(dr), B, C, T, V, _stream(x))
+    _lib.check(rc, "sgcn_bn_bwd_apply_tsh")
+    return dx, dr
 
 
 def mask_prep(mask):

@@ -47,7 +47,8 @@ OP_CLASSES = {
     "bn_stats": (("moments_kernel", "moments_ja_kernel"), ()),
     "bn_apply": (("bn_apply_kernel", "bn_apply_ja_kernel"), ()),
     "bn_bwd_reduce": (("bn_bwd_reduce_kernel", "bn_bwd_reduce_ja_kernel"), ()),
-    "bn_bwd_apply": (("bn_bwd_apply_kernel", "bn_bwd_apply_ja_kernel"), ()),
+    "bn_bwd_apply": (("bn_bwd_apply_kernel", "bn_bwd_apply_ja_kernel",
+                      "bn_bwd_apply_tsh_kernel"), ()),
     "gcn_dx_finish": (("gcn_dx_finish_kernel", "gcn_dx_finish_ja_kernel"), ()),
     "gcn_gather": (("gcn_gather_kernel",), ()),
     "finalize": (("bn_finalize_kernel", "bn_eval_coef_kernel", "bn_bwd_finalize_kernel",
