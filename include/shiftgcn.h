@@ -56,7 +56,8 @@ extern "C" {
  * sgcn_pw_fwd_bf16 (eval-mode bf16-operand contractions) and sgcn_clip_augment (the feeder's
  * training augmentations on the device); sgcn_bn_bwd_apply_tsh, and sgcn_tshift_bwd_gbn
  * accepting gin = NULL (shift_in's input gradient inside a unit is never stored: the
- * sums-only form, and the apply that re-forms the gradient from gout). */
+ * sums-only form, and the apply that re-forms the gradient from gout); the evaluation phase
+ * sgcn_score_metrics, sgcn_batch_loss and sgcn_ce_bwd. */
 int sgcn_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -597,6 +598,57 @@ int sgcn_mask_prep_many(const float* const* mask, float* const* m, const int* co
 int sgcn_mask_grad_finalize_many(const float* const* part, const float* const* mask,
                                  float* const* dmask, const int* B, const int* C,
                                  const int* V, int n, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Evaluation (main.py:450-515 `eval`, ensemble.py:18-32): loss, top-k, confusion matrix and
+ * score fusion of a batch of class scores, without a host round trip
+ * ------------------------------------------------------------------------------------ */
+#define SGCN_EVAL_MAX_STREAMS 8
+#define SGCN_EVAL_MAX_K 8
+
+/* ONE launch per batch of scores. scores: (S, n, C) float32 (f64 = 0) or float64 (f64 = 1),
+ * stream s at scores + s*stream_stride elements, S in 1..SGCN_EVAL_MAX_STREAMS; alpha: HOST
+ * array of S weights (may be NULL for S = 1), k: HOST array of nk <= SGCN_EVAL_MAX_K values;
+ * both travel as kernel arguments. labels: (n) int64. Per sample i, written at row
+ * row_offset + i of the run's buffers:
+ *   r = scores[0][i] (S = 1), else r[c] = ((s0[c]*a0 + s1[c]*a1) + s2[c]*a2) + ... left to
+ *     right in the scores' type, every product and sum rounded once (no FMA): ensemble.py:27
+ *     on numpy arrays of that type, bit for bit; stored to fused (scores' type, C per row)
+ *     when fused != NULL;
+ *   loss = logsumexp(r) - r[label] in float64 for either score type, the maximum m
+ *     subtracted first: s = sum over c != pred of exp(r[c] - m) (a fixed order),
+ *     lse = m + log1p(s), loss = log1p(s) + (m - r[label]) (no cancelling term, so small
+ *     losses keep their relative accuracy); both stored as float64;
+ *   pred (int32, optional) = the first index of the maximum (np.argmax);
+ *   rank (int32, optional) = #{c : r[c] > r[l]} + #{c > l : r[c] == r[l]}, l = label: the
+ *     sample is a top-k hit iff rank < k, i.e. l in np.argsort(r, kind="stable")[-k:].
+ *     Feeder.top_k / the reference's feeder use numpy's DEFAULT sort, which is unstable on
+ *     ties: the two agree exactly on rows without ties only.
+ * Counters (int32, integer device atomics, so the totals are order independent; all optional
+ * except hits when nk > 0; the caller zeroes them): hits[j] += (rank < k[j]);
+ * confusion[label*C + pred] += 1; a label outside [0, C) indexes nothing, gives loss = NaN
+ * and rank = C, leaves confusion and hits alone and adds 1 to bad_labels.
+ * NaN / Inf scores: the stored values are unspecified; nothing is accessed out of bounds.
+ * n = 0 returns 0 without a launch. */
+int sgcn_score_metrics(const void* scores, long long stream_stride, int S, const double* alpha,
+                       int f64, const long long* labels, int n, int C, long long row_offset,
+                       void* fused, double* loss, double* lse, int* pred, int* rank,
+                       const int* k, int nk, int* hits, int* confusion, int* bad_labels,
+                       void* stream);
+
+/* The batch mean of sgcn_score_metrics' losses, one small launch: the float64 sum of
+ * loss[row_offset .. row_offset + n) in a fixed tree (identical from run to run, no
+ * floating-point atomics) divided by n, written to batch_loss[batch_idx] (float64) and/or,
+ * rounded once, to *mean_f32; at least one of the two is given. n = 0: no launch. */
+int sgcn_batch_loss(const double* loss, long long row_offset, int n, double* batch_loss,
+                    long long batch_idx, float* mean_f32, void* stream);
+
+/* Backward of the mean cross-entropy: dlogits[i][c] = (exp(logits[i][c] - lse[i]) -
+ * [c == label[i]]) * g / n, g = *g a DEVICE float (the loss's output gradient: no host
+ * read), evaluated in float64 and rounded once to float32; rows whose label is outside
+ * [0, C) are zero. lse: sgcn_score_metrics' (n) float64. n = 0: no launch. */
+int sgcn_ce_bwd(const float* logits, const double* lse, const long long* labels, const float* g,
+                float* dlogits, int n, int C, void* stream);
 
 #ifdef __cplusplus
 }  /* extern "C" */

@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("SGCN_LIB_PATH", LIB_PATH)
 ABI_VERSION = 25
 BATCH_MAX = 32            # include/shiftgcn.h SGCN_BATCH_MAX
 SEQ_MAX_WM = 2048         # include/shiftgcn.h SGCN_SEQ_MAX_WM
+EVAL_MAX_STREAMS = 8      # include/shiftgcn.h SGCN_EVAL_MAX_STREAMS
+EVAL_MAX_K = 8            # include/shiftgcn.h SGCN_EVAL_MAX_K
 ABI_DIAG_FLAG = 0x10000   # include/shiftgcn.h SGCN_ABI_DIAG_FLAG: a diagnostic build
 EINVAL = -22
 
@@ -100,6 +102,10 @@ SIGNATURES = {
     "sgcn_tshift_pos_finalize_many": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "sgcn_mask_prep_many": (_I, [_P, _P, _P, _I, _P]),
     "sgcn_mask_grad_finalize_many": (_I, [_P, _P, _P, _P, _P, _P, _I, _P]),
+    "sgcn_score_metrics": (_I, [_P, _L, _I, _P, _I, _P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I,
+                                _P, _P, _P, _P]),
+    "sgcn_batch_loss": (_I, [_P, _L, _I, _P, _L, _P, _P]),
+    "sgcn_ce_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
 }
 
 
@@ -127,7 +133,7 @@ def _open(path):
             fn = getattr(lib, name)
         except AttributeError:
             # an entry added within the ABI version (sgcn_pw_fwd_bf16, sgcn_clip_augment,
-            # sgcn_bn_bwd_apply_tsh)
+            # sgcn_bn_bwd_apply_tsh, sgcn_score_metrics, sgcn_batch_loss, sgcn_ce_bwd)
             raise NativeLibraryError(
                 f"{path} (ABI {abi}) has no {name}: it was built from an older tree; "
                 "rebuild it") from None

@@ -6,6 +6,7 @@
 * :func:`adjust_learning_rate` — ``main.py:342-353`` (warm-up, step decay x0.1).
 * :func:`train_step` — ``main.py:397-416``: forward, CrossEntropy, zero_grad, backward,
   (data-parallel gradient reduction), optimizer step.
+* :func:`cross_entropy` — the loss on the project's own kernels (opt-in ``loss_fn``).
 """
 from __future__ import annotations
 
@@ -270,10 +271,20 @@ def adjust_learning_rate(optimizer, epoch, base_lr=0.1, steps=(60, 80, 100), war
     return lr
 
 
-def train_step(model, optimizer, x, label, grad_sync=None):
-    """One reference training iteration; returns the (device) loss tensor."""
+def cross_entropy(logits, labels):
+    """The mean cross-entropy on the project's own kernels (``shiftgcn.evaluate``:
+    ``sgcn_score_metrics`` + ``sgcn_batch_loss`` forward, ``sgcn_ce_bwd`` backward), float64
+    inside and summed in a fixed order; a ``loss_fn`` for :func:`train_step`."""
+    from .evaluate import cross_entropy as ce
+    return ce(logits, labels)
+
+
+def train_step(model, optimizer, x, label, grad_sync=None, loss_fn=None):
+    """One reference training iteration; returns the (device) loss tensor. ``loss_fn``:
+    ``(output, label) -> loss``; default ``torch.nn.functional.cross_entropy``
+    (:func:`cross_entropy` is the native form)."""
     output = model(x)
-    loss = torch.nn.functional.cross_entropy(output, label)
+    loss = (torch.nn.functional.cross_entropy if loss_fn is None else loss_fn)(output, label)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     if grad_sync is not None:
