@@ -7,6 +7,9 @@ import this package, and only as the checker / reported CPU baseline. The produc
 * :mod:`oracle.shift_oracle` — vectorised numpy restatement of the reference CUDA
   temporal-shift extension (``model/Temporal_shift/cuda/shift_cuda_kernel.cu``).
 * :mod:`oracle.shift_loops`  — scalar-loop restatement used to pin the vectorised one.
+* :mod:`oracle.ref_build`    — build recipe: the reference's own kernel templates compiled for
+  the host into ``oracle/_ref/`` (never committed); :mod:`oracle.shift_ref` loads them, and
+  ``tests/test_oracle_shift_ref.py`` holds the two restatements equal to them bit for bit.
 * :mod:`oracle.model_oracle` — PyTorch-eager CPU restatement of ``model/shift_gcn.py``
   (``tcn``, ``Shift_tcn``, ``Shift_gcn``, ``TCN_GCN_unit``, ``Model``) on top of the
   numpy shift, plus the reference training-step semantics (``main.py``).

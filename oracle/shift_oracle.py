@@ -22,13 +22,14 @@ stride != 1, computed in float32, is applied by the caller exactly as there).
 Index arithmetic (``floorf`` → int, bounds tests, C++ remainder/quotient for the
 stride-2 bottom backward) is reproduced bit-exactly.
 
-Parity pinning: the reference's CUDA extension cannot be built or run in this image
-(nvcc absent; its binding does not compile against torch 2.10; the prebuilt .so is
-CUDA 9 / sm_30 and is never loaded). This restatement is pinned by (a) a second,
-independent scalar-loop restatement in :mod:`oracle.shift_loops` checked element by
-element, (b) hand-derived known-answer vectors (integer shifts are exact
-translations; the reference ``demo.py`` case), and (c) the exact-adjoint property of
-the bottom backward, all in ``tests/test_oracle_shift.py``.
+Parity pinning: the reference's kernel templates (.cu:11-395) are compiled for the host by
+:mod:`oracle.ref_build` and this module is held equal to them bit for bit, in float32 and
+float64 (``tests/test_oracle_shift_ref.py``). The ATen host half
+(.cu:405-523) cannot be built here and stays restated (:func:`shift_backward`,
+:func:`reduce_position_grad`). Further pins: (a) a second, independent scalar-loop restatement
+in :mod:`oracle.shift_loops`, (b) hand-derived known-answer vectors (integer shifts are exact
+translations; the reference ``demo.py`` case), and (c) the exact-adjoint property of the
+bottom backward, all in ``tests/test_oracle_shift.py``.
 """
 from __future__ import annotations
 
@@ -92,6 +93,14 @@ def _bilinear(q11, q21, q12, q22, dx, dy, contract=False):
     return (((t1 + t2) + t3) + t4).astype(q11.dtype)
 
 
+def _dense(a: np.ndarray) -> np.ndarray:
+    """Results in C order, as the reference's ``at::zeros`` outputs are (.cu:408, 440, 480):
+    the gathers above leave the batch axis fastest-varying in memory, and torch-CPU
+    consumers of such a tensor reduce in another order (same values in, other roundings
+    out: the block and model fixtures are generated through this module)."""
+    return np.ascontiguousarray(a)
+
+
 def _frac(pos: np.ndarray):
     """Per-channel integer/fractional split: ``x1=floorf(x); dx=x-x1`` (.cu:49-71)."""
     i1 = _floor_int(pos)
@@ -122,7 +131,7 @@ def shift_forward(inp: np.ndarray, xpos: np.ndarray, ypos: np.ndarray, stride: i
     q22 = _taps(inp, hy2, wx2)
     dxb = dx[None, :, None, None]
     dyb = dy[None, :, None, None]
-    return _bilinear(q11, q21, q12, q22, dxb, dyb, contract)
+    return _dense(_bilinear(q11, q21, q12, q22, dxb, dyb, contract))
 
 
 def _taps_stride2_top(gout: np.ndarray, hh: np.ndarray, ww: np.ndarray) -> np.ndarray:
@@ -168,8 +177,8 @@ def shift_bottom_backward(gout: np.ndarray, xpos: np.ndarray, ypos: np.ndarray,
     q21 = tap(gout, hy1, wx2)
     q12 = tap(gout, hy2, wx1)
     q22 = tap(gout, hy2, wx2)
-    return _bilinear(q11, q21, q12, q22, dx[None, :, None, None], dy[None, :, None, None],
-                     contract)
+    return _dense(_bilinear(q11, q21, q12, q22, dx[None, :, None, None],
+                            dy[None, :, None, None], contract))
 
 
 def shift_position_backward(inp: np.ndarray, gout: np.ndarray, xpos: np.ndarray,
@@ -205,7 +214,7 @@ def shift_position_backward(inp: np.ndarray, gout: np.ndarray, xpos: np.ndarray,
     else:
         val_x = ((one - dyb) * (q21 - q11) + dyb * (q22 - q12)).astype(dt)
         val_y = ((one - dxb) * (q12 - q11) + dxb * (q22 - q21)).astype(dt)
-    return (val_x * gout).astype(dt), (val_y * gout).astype(dt)
+    return _dense((val_x * gout).astype(dt)), _dense((val_y * gout).astype(dt))
 
 
 def reduce_position_grad(g_bchw: np.ndarray) -> np.ndarray:

@@ -6,9 +6,12 @@ Run only where ``/root/reference`` exists (this build container):
 
 What runs: the reference's own ``model/shift_gcn.py`` modules and its
 ``model/Temporal_shift/cuda/shift.py`` autograd glue (imported from
-``/root/reference``), with the reference CUDA extension ``shift_cuda`` — which cannot be
-built or run here — replaced by a module whose ``forward``/``backward`` call the numpy
-restatement :mod:`oracle.shift_oracle` of ``shift_cuda_kernel.cu``. ``torch.zeros`` /
+``/root/reference``), with the reference CUDA extension ``shift_cuda`` — whose ATen half
+cannot be built here — replaced by a module whose ``forward``/``backward`` call the numpy
+restatement :mod:`oracle.shift_oracle` of ``shift_cuda_kernel.cu`` or, with
+``--reference-kernels DIR`` / :func:`use_kernels`, the reference's own kernel templates
+compiled for the host (:mod:`oracle.shift_ref`; ``tests/test_oracle_shift_ref.py`` holds the
+two equal on these cases). ``torch.zeros`` /
 ``torch.ones`` drop ``device='cuda'`` during construction (the CPU recipe the reference
 documents at ``CLAUDE.md:33``). Weights and inputs come from ``formula.py``; only
 outputs are stored. Nothing from the reference source is copied into the fixtures.
@@ -36,15 +39,39 @@ from oracle import shift_oracle as so  # noqa: E402
 import formula  # noqa: E402
 
 
+# which kernels stand behind ``shift_cuda``: "oracle" (the numpy restatement; how every
+# committed fixture was produced) or "reference" (the reference's own kernel templates compiled
+# for the host, oracle/shift_ref.py). The installed module looks this up at every call, so the
+# switch also reaches reference modules that were imported before it was thrown.
+_KERNELS = {"kind": "oracle"}
+
+
+def use_kernels(kind):
+    """Select the kernels behind ``shift_cuda``; returns the previous selection."""
+    if kind not in ("oracle", "reference"):
+        raise ValueError(kind)
+    if kind == "reference":
+        from oracle import shift_ref
+        shift_ref.shift_cuda_module()          # raises where the library is not built
+    prev, _KERNELS["kind"] = _KERNELS["kind"], kind
+    return prev
+
+
 def _install_shift_cuda():
     mod = types.ModuleType("shift_cuda")
 
     def forward(inp, xpos, ypos, stride):
+        if _KERNELS["kind"] == "reference":
+            from oracle import shift_ref
+            return shift_ref.shift_cuda_module().forward(inp, xpos, ypos, stride)
         out = so.shift_forward(inp.detach().numpy(), xpos.detach().numpy(),
                                ypos.detach().numpy(), stride)
         return torch.from_numpy(out)
 
     def backward(gout, inp, out, xpos, ypos, stride):
+        if _KERNELS["kind"] == "reference":
+            from oracle import shift_ref
+            return shift_ref.shift_cuda_module().backward(gout, inp, out, xpos, ypos, stride)
         gin, gx, gy = so.shift_backward(gout.detach().numpy(), inp.detach().numpy(),
                                         xpos.detach().numpy(), ypos.detach().numpy(), stride)
         return [torch.from_numpy(gin), torch.from_numpy(gx), torch.from_numpy(gy)]
@@ -288,19 +315,59 @@ def gen_models(ref_sg, out):
              if p.dtype.is_floating_point])
 
 
-def main():
-    torch.set_num_threads(max(1, os.cpu_count() or 1))
+def generate(out_dir, which=("shift", "block", "model")):
+    """Write the chosen fixture files into ``out_dir`` with the selected kernels."""
     ref_sg, ref_shift = _import_reference()
-    out = {}
-    gen_indices(ref_sg, out)
-    gen_shift(ref_shift, out)
-    np.savez_compressed(os.path.join(HERE, "shift_fixtures.npz"), **out)
-    out = {}
-    gen_blocks(ref_sg, out)
-    np.savez_compressed(os.path.join(HERE, "block_fixtures.npz"), **out)
-    out = {}
-    gen_models(ref_sg, out)
-    np.savez_compressed(os.path.join(HERE, "model_fixtures.npz"), **out)
+    if "shift" in which:
+        out = {}
+        gen_indices(ref_sg, out)
+        gen_shift(ref_shift, out)
+        np.savez_compressed(os.path.join(out_dir, "shift_fixtures.npz"), **out)
+    if "block" in which:
+        out = {}
+        gen_blocks(ref_sg, out)
+        np.savez_compressed(os.path.join(out_dir, "block_fixtures.npz"), **out)
+    if "model" in which:
+        out = {}
+        gen_models(ref_sg, out)
+        np.savez_compressed(os.path.join(out_dir, "model_fixtures.npz"), **out)
+
+
+def compare(out_dir, which=("shift", "block", "model")):
+    """Every array of the committed files against the ones in ``out_dir``: a list of
+    (file, key, what differs); empty when all are bit-equal."""
+    diffs = []
+    for w in which:
+        f = f"{w}_fixtures.npz"
+        a, b = np.load(os.path.join(HERE, f)), np.load(os.path.join(out_dir, f))
+        if sorted(a.files) != sorted(b.files):
+            diffs.append((f, "*", "key sets differ"))
+        for k in a.files:
+            if k in b.files and not (a[k].dtype == b[k].dtype and a[k].shape == b[k].shape
+                                     and a[k].tobytes() == b[k].tobytes()):
+                u, v = a[k], b[k]
+                same = u.shape == v.shape and u.dtype.kind == "f"
+                diffs.append((f, k, f"max |diff| {np.abs(u - v).max():.3e}" if same else "differs"))
+    return diffs
+
+
+def main():
+    """``gen_fixtures.py``: rewrite the committed files with the restatement behind
+    ``shift_cuda``. ``gen_fixtures.py --reference-kernels DIR``: write them into DIR with the
+    compiled reference kernels instead and report every array that differs from the
+    committed ones (nothing committed is touched)."""
+    torch.set_num_threads(max(1, os.cpu_count() or 1))
+    if len(sys.argv) > 1 and sys.argv[1] == "--reference-kernels":
+        out_dir = sys.argv[2]
+        os.makedirs(out_dir, exist_ok=True)
+        use_kernels("reference")
+        generate(out_dir)
+        diffs = compare(out_dir)
+        for d in diffs:
+            print("DIFF", *d)
+        print(f"{len(diffs)} arrays differ from the committed fixtures")
+        sys.exit(1 if diffs else 0)
+    generate(HERE)
     for f in ("shift_fixtures.npz", "block_fixtures.npz", "model_fixtures.npz"):
         print(f, os.path.getsize(os.path.join(HERE, f)), "bytes")
 

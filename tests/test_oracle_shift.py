@@ -1,6 +1,7 @@
 """Pin the temporal-shift oracle (CPU; no GPU needed).
 
-The reference CUDA extension cannot run here, so the restatement is pinned by:
+tests/test_oracle_shift_ref.py holds the restatement equal to the reference's own kernel
+code compiled for the host; here it is pinned, independently of that build, by:
 (1) a second, scalar-loop restatement (bit-exact agreement), (2) hand-derived known
 answers, (3) the exact-adjoint property of the bottom backward (float64), and (4) the
 fixtures produced through the reference's own ``ShiftFunction`` glue (``shift.py``).
